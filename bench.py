@@ -13,22 +13,28 @@ One "step" = one pass of the hot path over one batch: ray gather (GPU-resident t
 forward, all losses, fused backward, (all-reduce), Adam + LinearLR.  Inputs are resident in HBM when
 the timed region starts.  Multi-GPU: STRONG scaling by default -- one global batch of --rays rays per step, split N ways, one
 all-reduce of the flat gradient (BASELINE configs[2]); the same run also times the weak-scaled step (--rays per rank) and
-reports it beside the headline.  The N = 1 line carries `predicted_scaling`: the measured single-GPU step at rays / N for N = 2, 4, 8
+reports it beside the headline (--full).  --full --predicted-scaling adds `predicted_scaling`: the measured single-GPU step at rays / N for N = 2, 4, 8
 with the step's collective in place (a one-rank RCCL group: two graph segments with the all-reduce between them).
 
-Rank 0 writes the FULL record (every sub-record and kernel table) to gpurun_out/bench_full.json (--full-record) and prints, as the LAST
-stdout line, ONE compact JSON object under 4 KB (`headline_line`): the contract's keys, `roofline`, `cpu_baseline`, and three numbers per
-extra leg.  `dtype` names the arithmetic of the timed step as the library's planner ran it: "bf16+fp8stage" = bf16 MLP contractions whose
-layer inputs / output gradients cross HBM as e4m3 / e5m2 on their way to the weight-gradient kernel (which contracts them on the MX-fp8
-matrix path), "bf16" = the same with bf16 staging, "f32" = the 1e-5 parity mode.  `roofline` is for the kernel with the largest share of
-the step, measured with HIP events on the launch stream inside the library (nca_timing_*) over an eager pass of the same step (events
-cannot be recorded inside a replayed graph: the table decomposes `eager_ms_per_step`); fractions are named by their denominator --
-`mfma_frac` (dense MFMA peak of the pipe the contractions run on: 2 500 TFLOP/s bf16; 2 500 / 6 for the f32 mode, whose hidden layers are six
-bf16 products per f32 product) and `hbm_frac` (8 TB/s).  `cpu_baseline` is the CPU oracle (reference-equivalent torch CPU ops) on a bounded
-sample.  At N = 1 the default run also times: `baseline_config_dtype` (stage_fp8 = 0: BASELINE configs[1] as written -- bf16 operands
-everywhere, nothing in 8 bits), `f32`, `latency_regime` (the reference's default batch, 1 024 rays x 500 samples), `configs3` (MAGIX 512^2 x
-256, f32), `sustained` and `unfused_gpu_baseline` (the reference-equivalent torch ops run op by op on the same GPU: the denominator of the
-north star's >= 10x).  --no-extras drops those; --psnr-steps N and --predicted-scaling add their records to the full record.
+A plain run does what its headline figure needs and nothing more: set up, warm up, time --steps steps, write the last step's outputs
+if --dump-outputs DIR is given (DIR/<name>.npy: loss, pixel loss, loss terms, the parameters of both nets; the inputs are seeded, so two
+builds can be compared output for output) and print ONE compact JSON line: `metric`, `value` (rays/s), `unit`, `higher_is_better`,
+`ms_per_step` (wall time of one timed step), `dtype` and the configuration.  `dtype` names the arithmetic of the timed step as the library's
+planner ran it: "bf16+fp8stage" = bf16 MLP contractions whose layer inputs / output gradients cross HBM as e4m3 / e5m2 on their way to the
+weight-gradient kernel (which contracts them on the MX-fp8 matrix path), "bf16" = the same with bf16 staging, "f32" = the 1e-5 parity mode.
+
+--full adds everything else, and rank 0 then writes the FULL record (every sub-record and kernel table) to bench_out/bench_full.json
+(--full-record) and prints, as the LAST stdout line, the compact line (`headline_line`, under 4 KB) with `roofline`, `cpu_baseline` and
+three numbers per extra leg.  `roofline` is for the kernel with the largest share of the step, measured with HIP events on the launch
+stream inside the library (nca_timing_*) over an eager pass of the same step (events cannot be recorded inside a replayed graph: the
+table decomposes `eager_ms_per_step`); fractions are named by their denominator -- `mfma_frac` (dense MFMA peak of the pipe the
+contractions run on: 2 500 TFLOP/s bf16; 2 500 / 6 for the f32 mode, whose hidden layers are six bf16 products per f32 product) and
+`hbm_frac` (8 TB/s).  `cpu_baseline` is the CPU oracle (reference-equivalent torch CPU ops) on a bounded sample.  At N = 1 a --full run
+also times: `baseline_config_dtype` (stage_fp8 = 0: BASELINE configs[1] as written -- bf16 operands everywhere, nothing in 8 bits), `f32`,
+`latency_regime` (the reference's default batch, 1 024 rays x 500 samples), `configs3` (MAGIX 512^2 x 256, f32), `sustained` and
+`unfused_gpu_baseline` (the reference-equivalent torch ops run op by op on the same GPU: the denominator of the north star's >= 10x);
+with N > 1 it also times the other scaling mode.  --no-extras drops those; --psnr-steps N and --predicted-scaling add their records to
+the full record.
 """
 import argparse
 import hashlib
@@ -75,6 +81,10 @@ def parse(argv=None):
     ap.add_argument("--samples", type=int, default=192)
     ap.add_argument("--prec", default="bf16", choices=["f32", "bf16"],
                     help="bf16 = BASELINE configs[1] (bf16 MFMA operands, f32 accumulate/master weights, PSNR-gated); f32 = parity mode")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure: the eager pass that times the kernels (roofline), the CPU baseline, "
+                    "the extra legs (--no-extras drops those) and the full record (--full-record).  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the timed step returned in its last step (loss, "
+                    "pixel loss, the loss terms) and the parameters it left behind, as DIR/<name>.npy in float32 / float64")
     ap.add_argument("--cpu-rays", type=int, default=2048, help="rays per step of the CPU baseline sample")
     ap.add_argument("--cpu-steps", type=int, default=5, help="timed CPU steps (plus one warm-up): ~20 s of CPU work at the defaults")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -93,8 +103,8 @@ def parse(argv=None):
                     "0 = skip, the default: the PSNR evidence is tests/test_psnr_gates.py)")
     ap.add_argument("--predicted-scaling", action="store_true", help="add `predicted_scaling` to the full record: the measured one-GPU step of a rank's share (rays / N, N = 2, 4, 8) "
                     "under a one-rank RCCL group; the links' time in it is an ESTIMATE")
-    ap.add_argument("--full-record", default=None, help="where the full record goes (default: gpurun_out/bench_full.json under the repository root); the LAST stdout "
-                    "line is the compact headline record (< 4 KB) whatever this says")
+    ap.add_argument("--full-record", default=None, help="where the full record of a --full run goes (default: bench_out/bench_full.json under the repository root); "
+                    "the LAST stdout line is the compact headline record (< 4 KB) whatever this says")
     ap.add_argument("--configs3-steps", type=int, default=3, help="timed steps of the BASELINE configs[3] sub-record (MAGIX geometry, 8 sequences x 10 phases of 512^2, "
                     "256 samples per ray, f32, one full detector = 262 144 rays per step; 0: skip)")
     ap.add_argument("--latency-steps", type=int, default=200, help="timed steps of the latency-regime sub-record (the reference's default batch: 1 024 rays x 500 "
@@ -350,9 +360,9 @@ BWD_MODES = {1: "mode 1: recompute backward (no forward store)", 3: "mode 3: fro
 STORE_NAMES = {0: "none", 1: "f32", 3: "8-bit staged (e4m3 layer inputs)", 4: "bf16 (bf16 layer inputs)"}
 
 
-def measure(args, prec, stage_fp8, data, dev, rank, world, use_pg, steps, warmup, sustained_steps=0):
-    """Warm-up, `steps` timed steps between barriers (max over ranks), then an eager pass that times the kernels with HIP
-    events, then (optionally) the sustained run.  `stage_fp8`: None = the planner's default, 0 / 1 = this record's
+def measure(args, prec, stage_fp8, data, dev, rank, world, use_pg, steps, warmup, sustained_steps=0, outputs=False):
+    """Warm-up, `steps` timed steps between barriers (max over ranks), then (--full) an eager pass that times the kernels with HIP
+    events, then (optionally) the sustained run.  `outputs`: the record carries the last timed step's outputs (step_outputs).  `stage_fp8`: None = the planner's default, 0 / 1 = this record's
     trainer runs with that value of NCA_OPT_STAGE_FP8 as ITS planner option (per trainer: nothing process-wide is touched).  Returns
     the record's fields (value, ms_per_step, dtype label, plan, roofline, ...).  A forward store that cannot be allocated is an
     error here (fused.STRICT_STORE): the bench never silently times the recompute path."""
@@ -360,12 +370,12 @@ def measure(args, prec, stage_fp8, data, dev, rank, world, use_pg, steps, warmup
     strict0 = fused_mod.STRICT_STORE
     fused_mod.STRICT_STORE = True
     try:
-        return _measure(args, prec, stage_fp8, data, dev, rank, world, use_pg, steps, warmup, sustained_steps)
+        return _measure(args, prec, stage_fp8, data, dev, rank, world, use_pg, steps, warmup, sustained_steps, outputs)
     finally:
         fused_mod.STRICT_STORE = strict0
 
 
-def _measure(args, prec, stage_fp8, data, dev, rank, world, use_pg, steps, warmup, sustained_steps):
+def _measure(args, prec, stage_fp8, data, dev, rank, world, use_pg, steps, warmup, sustained_steps, outputs=False):
     from nerfca_amd import _capi
     from nerfca_amd import fused as fused_mod
     tr = make_trainer(args, prec, data, dev, rank, world, use_pg, plan_opts=None if stage_fp8 is None else {"stage_fp8": stage_fp8})
@@ -398,9 +408,10 @@ def _measure(args, prec, stage_fp8, data, dev, rank, world, use_pg, steps, warmu
     _capi.timing_enable(not args.graph)
     t0 = time.perf_counter()
     for i in range(steps):
-        loss, _, _ = step(base_iter + warmup + i)
+        loss, pixel, terms = step(base_iter + warmup + i)
     barrier()
     dt = time.perf_counter() - t0
+    dumped = step_outputs(tr, loss, pixel, terms) if outputs else None       # (before anything below steps the trainer again)
     loss = float(loss)
     plan = tr.plan()            # of this trainer's last backward (graph: of the capture)
     sustained = None
@@ -417,7 +428,7 @@ def _measure(args, prec, stage_fp8, data, dev, rank, world, use_pg, steps, warmu
                      "in_kernel_clock": "profiles/r03_clock_probe.txt (round 3's diagnostic build that stamps s_memtime / s_memrealtime -- tools/r03_experiments.sh; no stamp executes in this build)"}
     timed_steps, eager_dt = steps, dt
     eager_ms = None
-    if args.graph:       # events cannot be recorded inside a replayed graph: time the same kernels eagerly, outside dt
+    if args.graph and args.full:       # events cannot be recorded inside a replayed graph: time the same kernels eagerly, outside dt
         timed_steps = max(1, min(args.kernel_steps, steps))
         tr.step(base_iter)          # (untimed: the eager step's first pass allocates its own store, and first-touch page mapping shows in the kernels)
         tr.step(base_iter + 1)
@@ -436,7 +447,7 @@ def _measure(args, prec, stage_fp8, data, dev, rank, world, use_pg, steps, warmu
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         dt = float(tmax.item())
-    kern = kernel_table(args, timed_steps, plan, world)
+    kern = kernel_table(args, timed_steps, plan, world) if args.full else None        # (per-kernel figures: --full runs only)
     _capi.timing_reset()
     fp8 = bool(plan.get("stage_fp8"))
     label = "f32" if prec == "f32" else ("bf16+fp8stage" if fp8 else "bf16")
@@ -448,22 +459,43 @@ def _measure(args, prec, stage_fp8, data, dev, rank, world, use_pg, steps, warmu
                           "bf16+fp8stage": "bf16 MFMA operands for the MLP contractions (forward and dgrad), f32 accumulation, f32 master weights; the layer inputs (e4m3) and output "
                                            "gradients (e5m2, per-tile power-of-two scale) cross HBM in 8 bits and the weight gradient contracts them on the MX-fp8 matrix path; PSNR-gated "
                                            "(tests/test_psnr_gates.py)"}[label],
-           "hip_graph": bool(args.graph), "eager_ms_per_step": eager_ms, "kernel_table_steps": timed_steps, "final_loss": loss,
+           "hip_graph": bool(args.graph), "eager_ms_per_step": eager_ms, "kernel_table_steps": timed_steps if kern else None, "final_loss": loss,
            "plan": {"stage_fp8": fp8, "backward": BWD_MODES.get(plan.get("bwd_kernel_mode"), str(plan.get("bwd_kernel_mode"))),
                     "forward_store": STORE_NAMES.get(plan.get("fwd_store_format", 0) & 15, str(plan.get("fwd_store_format"))),
                     "resident_weight_images": {"fwd": bool(plan.get("fwd_resident")), "bwd": bool(plan.get("bwd_resident"))},
                     "ray_chunks": plan.get("chunks"),
                     "wgrad": {"jobs": plan.get("wgrad_jobs"), "splits": plan.get("wgrad_splits"), "splits_rebuild_jobs": plan.get("wgrad_splits_rebuild")},
                     "overlap": {"cus": plan.get("overlap_cus"), "forked": bool(plan.get("overlap_forked"))},
-                    "launches_per_step": {k: (kern[k]["launches"] // max(timed_steps, 1)) for k in ("fwd", "bwd_dgrad", "bwd_wgrad")}},
-           "roofline": roofline_of(args, prec, kern, eager_dt, plan, dt / steps * 1e3, world),
+                    "launches_per_step": {k: (kern[k]["launches"] // max(timed_steps, 1)) for k in ("fwd", "bwd_dgrad", "bwd_wgrad")} if kern else None},
+           "roofline": roofline_of(args, prec, kern, eager_dt, plan, dt / steps * 1e3, world) if kern else None,
            "store_fallbacks": fused_mod.STORE_FALLBACKS - fallbacks0}       # > 0: some backward ran on the recompute path (store did not fit)
     if sustained:
         rec["sustained"] = sustained
+    if dumped is not None:
+        rec["outputs"] = dumped
     tr.check_ray_ids()          # (one device read: a ray id outside the table would have been clamped by nca_prepare_batch -- never silently)
     del tr
     torch.cuda.empty_cache()
     return rec
+
+
+def step_outputs(tr, loss, pixel, terms):
+    """What a caller of the timed step holds after its last call, copied to the host: the step's return values (loss, pixel loss, the
+    loss terms) and the parameters it left in both nets.  float64 stays float64, every other dtype becomes float32; < 1 MB by default."""
+    if isinstance(terms, (list, tuple)):
+        terms = torch.stack([torch.as_tensor(x, device=loss.device).reshape(()).double() for x in terms])
+    out = {"loss": loss, "pixel_loss": pixel, "terms": terms}
+    for tag, m in (("static", tr.s), ("dynamic", tr.t)):
+        for k, p in m.named_parameters():
+            out[f"{tag}.{k}"] = p
+    return {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32).contiguous().numpy() for k, v in out.items()}
+
+
+def write_outputs(path, outputs):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in outputs.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def quick_step_ms(args, prec, data, dev, rank, world, use_pg, global_rays, steps=30, warmup=5):
@@ -693,7 +725,7 @@ def precision_summary(rec):
 
 def write_full_record(args, out):
     """The full record (every sub-record, every kernel table) goes to a FILE; stdout ends with the compact line the driver parses."""
-    path = args.full_record or os.path.join(ROOT, "gpurun_out", "bench_full.json")
+    path = args.full_record or os.path.join(ROOT, "bench_out", "bench_full.json")
     try:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         with open(path, "w") as f:
@@ -709,19 +741,20 @@ HEADLINE_LIMIT_BYTES = 4000
 
 
 def headline_line(out, full_path=None):
-    """The LAST stdout line: the bench contract's keys plus `roofline` and `cpu_baseline`, under HEADLINE_LIMIT_BYTES (round 5's 24.6 KB line was
+    """The LAST stdout line: the bench contract's keys plus (--full) `roofline` and `cpu_baseline`, under HEADLINE_LIMIT_BYTES (round 5's 24.6 KB line was
     not parsed by the driver).  Everything else is in the full record (`full_record`).  tests/test_host_cpu.py checks size, keys and json.loads."""
     cfg = out["config"]
-    roof = out["roofline"]
+    roof = out.get("roofline")
     line = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data")}
     line["config"] = {"workload": cfg["workload"], "rays_per_step_per_gpu": cfg["rays_per_step_per_gpu"], "global_rays_per_step": cfg["global_rays_per_step"],
                       "samples_per_ray": cfg["samples_per_ray"], "parallelism": cfg["parallelism"], "hip_graph": cfg["hip_graph"], "stage_fp8": cfg["stage_fp8"],
                       "launches_per_step": cfg["launches_per_step"]}
-    line["roofline"] = {"bound": roof["bound"], "kernel": roof["kernel"], "achieved": roof["achieved"], "peak": roof["peak"], "unit": roof["unit"], "frac": roof["frac"],
-                        "traffic": roof.get("traffic"), "avg_launch_ms": roof["avg_launch_ms"], "launches": roof["launches"],
-                        "step": {k: roof["step"][k] for k in ("achieved", "peak", "unit", "frac")}, "kernels": _kernel_fracs(roof)}
-    if roof.get("traffic_source"):
-        line["roofline"]["traffic_source"] = roof["traffic_source"]["file"]
+    if roof:          # (--full runs: the per-kernel figures come from an eager pass of their own)
+        line["roofline"] = {"bound": roof["bound"], "kernel": roof["kernel"], "achieved": roof["achieved"], "peak": roof["peak"], "unit": roof["unit"], "frac": roof["frac"],
+                            "traffic": roof.get("traffic"), "avg_launch_ms": roof["avg_launch_ms"], "launches": roof["launches"],
+                            "step": {k: roof["step"][k] for k in ("achieved", "peak", "unit", "frac")}, "kernels": _kernel_fracs(roof)}
+        if roof.get("traffic_source"):
+            line["roofline"]["traffic_source"] = roof["traffic_source"]["file"]
     if "cpu_baseline" in out:
         line["cpu_baseline"] = {k: out["cpu_baseline"][k] for k in ("value", "unit", "cores", "kind", "sample")}
     b = out.get("baseline_config_dtype")
@@ -797,10 +830,11 @@ def main():
 
     views = synthetic.TRAIN_VIEWS if args.views == 4 else synthetic.TRAIN_VIEWS_8[: args.views]
     data = synthetic.make_dataset(args.det, args.samples, dev, views=views)
+    extras = args.full and not args.no_extras      # a plain run times the headline step and nothing else
     main_rec = measure(args, args.prec, None, data, dev, rank, world, use_pg, args.steps, args.warmup,
-                       sustained_steps=args.sustained_steps if (world == 1 and not args.no_extras) else 0)
+                       sustained_steps=args.sustained_steps if (world == 1 and extras) else 0, outputs=bool(args.dump_outputs) and rank == 0)
     other_rec = None
-    if (world > 1 or os.environ.get("NERFCA_FORCE_PG") == "1") and not args.no_extras:          # (the env switch: the multi-rank legs on a one-GPU box)
+    if (world > 1 or os.environ.get("NERFCA_FORCE_PG") == "1") and extras:          # (the env switch: the multi-rank legs on a one-GPU box)
         # the other scaling mode in the same run, every rank taking part: strong = one global batch of --rays split N ways, weak = --rays per rank
         other = "weak" if args.scaling == "strong" else "strong"
         g_rays = args.rays * world if other == "weak" else args.rays
@@ -810,6 +844,8 @@ def main():
                          "rays_per_step_per_gpu": g_rays // world, "steps": 30, "warmup": 5}
 
     if rank == 0:
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, main_rec.pop("outputs"))
         out = {"metric": f"training rays/sec ({args.det}^2 det, {args.samples} samples/ray)", "value": main_rec["value"], "unit": "rays/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": main_rec["ms_per_step"],
                "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": main_rec["dtype"], "data": "synthetic",
@@ -826,11 +862,11 @@ def main():
             out["sustained"] = main_rec["sustained"]
         if other_rec is not None:
             out[other_rec["scaling"] + "_scaling"] = other_rec
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, data)
-        if world == 1 and not args.no_extras and args.prec == "bf16" and args.predicted_scaling:
+        if world == 1 and extras and args.prec == "bf16" and args.predicted_scaling:
             out["predicted_scaling"] = predicted_scaling(args, data, dev, main_rec["ms_per_step"])
-        if world == 1 and not args.no_extras:
+        if world == 1 and extras:
             if args.unfused_gpu_rays > 0:
                 out["unfused_gpu_baseline"] = unfused_gpu_baseline(args, data)
                 out["vs_unfused_gpu"] = out["value"] / out["unfused_gpu_baseline"]["value"]
@@ -857,7 +893,7 @@ def main():
                 out["latency_regime"] = latency_record(args, dev)
             if args.prec == "bf16":
                 out["general_kernels"] = general_kernels_record()
-        path = write_full_record(args, out)
+        path = write_full_record(args, out) if args.full else None
         print(headline_line(out, path), flush=True)
     if use_pg:
         torch.distributed.destroy_process_group()

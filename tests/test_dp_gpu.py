@@ -186,7 +186,7 @@ def test_bench_over_rccl_with_one_rank():
     """bench.py's N > 1 code path on the one-GPU box: RCCL process group of one rank (NERFCA_FORCE_PG=1), gradient all-reduce
     every step, barriers, max-over-ranks time -- in a child process, as the driver runs it."""
     port = str(_free_port())
-    line = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--rays", "8192", "--no-cpu-baseline", "--no-extras"],
+    line = _bench(["--gpus", "1", "--full", "--steps", "2", "--warmup", "1", "--rays", "8192", "--no-cpu-baseline", "--no-extras"],
                   {"NERFCA_FORCE_PG": "1", "RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": port})
     assert line["rccl_ranks"] == 1 and line["n_gpus"] == 1 and line["value"] > 0
 
@@ -197,5 +197,5 @@ def test_bench_self_launch_two_gpus():
     GPU), they train over RCCL, rank 0's line comes back.  Needs two GPUs."""
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs")
-    line = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], {})
+    line = _bench(["--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], {})
     assert line["rccl_ranks"] == 2 and line["n_gpus"] == 2 and line["config"]["parallelism"] == "ray-sharded dp2"

@@ -24,7 +24,7 @@ def main():
     for w in [int(x) for x in args.values.split(",")]:
         env = dict(os.environ, NCA_WGRAD_W=str(w))
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rays", str(args.rays), "--samples", str(args.samples), "--steps", "10", "--warmup", "3",
-                              "--no-extras", "--no-cpu-baseline", "--kernel-steps", "8"], env=env, capture_output=True, text=True, timeout=600)
+                              "--full", "--no-extras", "--no-cpu-baseline", "--kernel-steps", "8"], env=env, capture_output=True, text=True, timeout=600)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if out.returncode != 0 or not line:
             print(f"W = {w}: failed\n{out.stderr[-400:]}")

@@ -5,7 +5,7 @@
 for LIB in _cus; do
   L=nerf-ca_amd/lib/libnerfca_hip$LIB.so; [ -f $L ] || continue
   for K in 256 192 128 64; do
-    NCA_CUS=$K NERFCA_LIB=$PWD/$L timeout -k 10 200 python3 bench.py --eager --steps 6 --warmup 2 --no-extras --no-cpu-baseline > /tmp/cus.json 2>/dev/null || { echo "lib$LIB cus $K failed"; continue; }
+    NCA_CUS=$K NERFCA_LIB=$PWD/$L timeout -k 10 200 python3 bench.py --full --eager --steps 6 --warmup 2 --no-extras --no-cpu-baseline > /tmp/cus.json 2>/dev/null || { echo "lib$LIB cus $K failed"; continue; }
     python3 - "$K" "lib$LIB" <<'PY'
 import json, sys
 b = json.loads([l for l in open("/tmp/cus.json") if l.startswith("{")][-1]); k = b["roofline"]["all_kernels"]
