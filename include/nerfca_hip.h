@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define NCA_ABI_VERSION 12
+#define NCA_ABI_VERSION 13
 
 enum {
     NCA_OK = 0,
@@ -292,6 +292,40 @@ int nca_loss_fwd_bwd(const NcaLoss* desc, const double* pix, const double* gt, c
                      const float* sig_s, const float* sig_d, const double* dists,
                      double* terms, double* g_pix, float* g_sig_s, float* g_sig_d,
                      void* work, int64_t work_bytes, void* stream);
+
+/* ---- the static-only loop's loss (ABI 13): weighted_MSELoss + compute_occl_loss + the loss assembly of train/run_nerf.py:227-230 and their
+ *      autograd for ONE field, in one pass per ray (StaticTrainer.step_fused / step_graph / evaluate):
+ *        pixel = inv_R sum_r wpix[r] (pix[r] - gt[r])^2
+ *        occl  = inv_R sum_r sum_s (double)sigma[r,s] dists[s]
+ *        loss  = pixel + w_occl occl
+ *        g_pix[r] = 2 wpix[r] (pix[r] - gt[r]) inv_R        g_sigma[r,s] = (float)(w_occl inv_R dists[s])
+ *      sigma is the UN-scaled density of render_volume_density (train/model_helpers.py:86-97; NcaRays.single_field).  occl_reg_perc does
+ *      not appear: compute_occl_loss (train/model_helpers.py:226-248) ORs an all-ones back mask into the front mask unless use_back is
+ *      passed and run_nerf.py:228 never passes it, so the term is the mean ray sum whatever the percentage.  Every sum runs in f64 (sigma
+ *      f32, dists f64: the reference's dtype promotion), per-block partials and one finishing block in fixed order: results are
+ *      bit-identical run to run and with or without the gradient outputs. */
+typedef struct NcaStaticLoss {
+    int64_t R;               /* rays of this batch (this rank's slice under data parallelism)          */
+    int32_t S;
+    int32_t reserved;
+    double w_occl;           /* run_args.occl_weight_start (train/run_nerf.py:230): constant over a run */
+    double inv_R;            /* 1 / GLOBAL ray count                                                    */
+    float* terms_f32;        /* NULL, or DEVICE f32[NCA_ST_COUNT]: the terms once more as f32 (they ride behind the flat gradient in an all-reduce) */
+    /* optional, zero = unused: pix formed from the forward's per-tile ray sums, exactly as NcaLoss.ray_part / ray_I0 / ray_nchunk / pix_out */
+    const double* ray_part;
+    const float* ray_I0;
+    double* pix_out;
+    int32_t ray_nchunk;
+    int32_t reserved2;
+} NcaStaticLoss;
+enum { NCA_ST_LOSS = 0, NCA_ST_PIXEL, NCA_ST_OCCL, NCA_ST_COUNT = 4 };   /* [3] reserved, written 0 */
+int64_t nca_static_loss_workspace(int64_t R);
+/* terms f64[NCA_ST_COUNT]; g_pix f64[R] and g_sigma f32[R,S] (both NULL = values only); pix, gt, wpix f64[R] (pix is ignored with
+ * desc->ray_part); sigma f32[R,S]; dists f64[S]. */
+int nca_static_loss_fwd_bwd(const NcaStaticLoss* desc, const double* pix, const double* gt, const double* wpix,
+                            const float* sigma, const double* dists,
+                            double* terms, double* g_pix, float* g_sigma,
+                            void* work, int64_t work_bytes, void* stream);
 
 /* weighted_MSELoss.forward (train/model_helpers.py:284-288): out[r] = (pred[r] - gt[r])^2 * w[r] (the caller takes the mean,
  * train/run_composite.py:287) and its backward; all arrays of one dtype, f64 (is_f64 = 1: what the real script's f64 ray table gives) or

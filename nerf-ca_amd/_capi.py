@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("NERFCA_LIB") or os.path.join(_HERE, "lib", "libnerfca
 ENC_NONE, ENC_BANDS, ENC_FOURIER = 0, 1, 2
 ACT_SIGMOID, ACT_SOFTPLUS, ACT_CLAMP = 0, 1, 2
 PREC_F32, PREC_BF16 = 0, 1
-ABI_VERSION = 12
+ABI_VERSION = 13
 OPT_STAGE_FP8 = 1          # (0 is reserved: the retired bf16-staged backward's on-chip threshold)
 OPT_RESIDENT_MIN_TILES = 2
 OPT_STAGE_FP8_MIN_TILES = 3
@@ -31,6 +31,7 @@ KERNEL_KINDS = {"pack": K_PACK, "fwd": K_FWD, "bwd_dgrad": K_BWD_DGRAD, "bwd_wgr
                 "loss": K_LOSS, "adam": K_ADAM}
 TERM_NAMES = ["loss", "pixel", "blendw", "sigma_s_max", "sigma_d_max", "favor_s", "s_entropy", "s_entropy_sum", "d_entropy",
               "d_entropy_sum", "d_occl", "s_l1", "s_l2"]
+STATIC_TERM_NAMES = ["loss", "pixel", "occl", "reserved"]      # nca_static_loss_fwd_bwd (NCA_ST_*)
 
 
 NET_GENERAL = 0x10000      # NcaNet.reserved: run on the general kernels whatever the width
@@ -84,6 +85,12 @@ class NcaLoss(C.Structure):
                 # ABI 11 (zero = ABI 10 behaviour): pix formed by the loss kernel from the forward's per-tile ray sums; the terms once more as f32
                 ("ray_part", C.c_void_p), ("ray_I0", C.c_void_p), ("pix_out", C.c_void_p), ("ray_nchunk", C.c_int32), ("reserved2", C.c_int32),
                 ("terms_f32", C.c_void_p)]
+
+
+class NcaStaticLoss(C.Structure):
+    """The static-only loop's loss of one field (ABI 13, train/run_nerf.py:227-230)."""
+    _fields_ = [("R", C.c_int64), ("S", C.c_int32), ("reserved", C.c_int32), ("w_occl", C.c_double), ("inv_R", C.c_double), ("terms_f32", C.c_void_p),
+                ("ray_part", C.c_void_p), ("ray_I0", C.c_void_p), ("pix_out", C.c_void_p), ("ray_nchunk", C.c_int32), ("reserved2", C.c_int32)]
 
 
 class NcaAdam(C.Structure):
@@ -149,6 +156,8 @@ SYMBOLS = {
     "nca_composite_bwd": (C.c_int, [_I64, _I32, _I32, _I32, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nca_loss_workspace": (_I64, [_I64]),
     "nca_loss_fwd_bwd": (C.c_int, [C.POINTER(NcaLoss), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "nca_static_loss_workspace": (_I64, [_I64]),
+    "nca_static_loss_fwd_bwd": (C.c_int, [C.POINTER(NcaStaticLoss), _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "nca_weighted_sq_err": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P]),
     "nca_weighted_sq_err_bwd": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nca_fine_depths_workspace": (_I64, [_I64]),

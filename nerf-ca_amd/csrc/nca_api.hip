@@ -1612,6 +1612,40 @@ extern "C" int nca_loss_fwd_bwd(const NcaLoss* d, const double* pix, const doubl
     return NCA_OK;
 }
 
+// >>> static-only loop (run_nerf.py): not part of the composite f32 path, left out of f32_sources_sha (tools/psnr_cache.py)
+extern "C" int64_t nca_static_loss_workspace(int64_t R) {
+    if (R <= 0) return fail(NCA_E_INVALID, "empty ray batch");
+    return align_up(nca_static_loss_partials_bytes(R), 256);
+}
+
+extern "C" int nca_static_loss_fwd_bwd(const NcaStaticLoss* d, const double* pix, const double* gt, const double* wpix,
+                                       const float* sigma, const double* dists,
+                                       double* terms, double* g_pix, float* g_sigma,
+                                       void* work, int64_t work_bytes, void* stream) {
+    if (!d) return fail(NCA_E_INVALID, "static loss descriptor is NULL");
+    if (d->R <= 0 || d->S <= 0) return fail(NCA_E_INVALID, "empty ray batch");
+    if (d->ray_part) {           // pix is formed by the kernel from the single-field forward's per-tile ray sums
+        if (!d->ray_I0 || d->ray_nchunk <= 0) return fail(NCA_E_INVALID, "ray_part needs ray_I0 and ray_nchunk > 0");
+    } else if (!pix) return fail(NCA_E_INVALID, "pix is NULL and the descriptor carries no ray_part");
+    if (!sigma || !dists) return fail(NCA_E_INVALID, "sigma or dists is NULL");
+    if (!gt || !wpix || !terms) return fail(NCA_E_INVALID, "a static loss input pointer is NULL");
+    if ((g_pix == nullptr) != (g_sigma == nullptr)) return fail(NCA_E_INVALID, "give both gradient outputs or neither");
+    const int64_t need = nca_static_loss_workspace(d->R);
+    if (!work || work_bytes < need) return fail(NCA_E_WORKSPACE, "static loss workspace %lld < %lld bytes", (long long)work_bytes, (long long)need);
+    NcaStaticLossArgs a;
+    a.R = d->R; a.S = d->S; a.ray_nchunk = d->ray_nchunk;
+    a.w_occl = d->w_occl; a.inv_R = d->inv_R;
+    a.pix = d->ray_part ? nullptr : pix; a.gt = gt; a.wpix = wpix; a.sigma = sigma; a.dists = dists;
+    a.terms = terms; a.g_pix = g_pix; a.g_sigma = g_sigma;
+    a.partials = static_cast<double*>(work);
+    a.terms_f32 = d->terms_f32;
+    a.ray_part = d->ray_part; a.ray_I0 = d->ray_I0; a.pix_out = d->ray_part ? d->pix_out : nullptr;
+    Span sp(NCA_K_LOSS, (hipStream_t)stream);
+    HIPCHK(nca_launch_static_loss(a, (hipStream_t)stream));
+    return NCA_OK;
+}
+// <<< static-only loop
+
 extern "C" int nca_weighted_sq_err(int64_t R, int32_t is_f64, const void* pred, const void* gt, const void* w, void* out, void* stream) {
     if (R <= 0) return fail(NCA_E_INVALID, "empty ray batch");
     if (!pred || !gt || !w || !out) return fail(NCA_E_INVALID, "a pointer is NULL");

@@ -222,6 +222,24 @@ struct NcaCompositeArgs {
 };
 hipError_t nca_launch_composite(const NcaCompositeArgs& a, bool bwd, hipStream_t st);
 hipError_t nca_launch_loss(const NcaLossArgs& a, hipStream_t st);
+// >>> static-only loop (run_nerf.py): not part of the composite f32 path, left out of f32_sources_sha (tools/psnr_cache.py)
+// the static-only loop's loss (train/run_nerf.py:227-230): weighted MSE + w_occl * mean ray sum of ONE un-scaled field (NcaStaticLoss)
+struct NcaStaticLossArgs {
+    int64_t R;
+    int32_t S, ray_nchunk;
+    double w_occl, inv_R;
+    const double* pix; const double* gt; const double* wpix;
+    const float* sigma; const double* dists;
+    double* terms; double* g_pix; float* g_sigma;
+    double* partials;           // [ceil(R / 4)][2]: pixel and occlusion sums of each block's rays
+    float* terms_f32;           // null, or f32[4]: the terms once more as floats
+    const double* ray_part;     // null, or the forward's per-tile ray sums [R][ray_nchunk]: pix is formed here (NcaStaticLoss.ray_part)
+    const float* ray_I0;
+    double* pix_out;
+};
+hipError_t nca_launch_static_loss(const NcaStaticLossArgs& a, hipStream_t st);
+int64_t nca_static_loss_partials_bytes(int64_t R);
+// <<< static-only loop
 hipError_t nca_launch_wsqerr(int64_t R, bool f64, const void* pred, const void* gt, const void* w, void* out, hipStream_t st);
 hipError_t nca_launch_wsqerr_bwd(int64_t R, bool f64, const void* pred, const void* gt, const void* w, const void* g_out, void* g_pred, void* g_gt, void* g_w, hipStream_t st);
 struct NcaAdamArgs {

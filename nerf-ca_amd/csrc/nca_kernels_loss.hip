@@ -334,6 +334,104 @@ int64_t nca_loss_partials_bytes(int64_t R) {
     return nblocks * (NPART + 2) * (int64_t)sizeof(double);
 }
 
+// >>> static-only loop (run_nerf.py): not part of the composite f32 path, left out of f32_sources_sha (tools/psnr_cache.py)
+// ------------------------------------------------------------------------------------------
+// The static-only loop's loss (train/run_nerf.py:227-230) of ONE field, forward and gradient in one pass per ray:
+//
+//   pixel = inv_R sum_r wpix[r] (pix[r] - gt[r])^2                        (weighted_MSELoss(...).mean(), model_helpers.py:284-288)
+//   occl  = inv_R sum_r sum_s (double)sigma[r,s] dists[s]                 (sum(compute_occl_loss(sigma, dists, occl_reg_perc)), :226-248)
+//   loss  = pixel + w_occl occl;   g_pix[r] = 2 wpix[r] (pix[r] - gt[r]) inv_R;   g_sigma[r,s] = (float)(w_occl inv_R dists[s])
+//
+// sigma is the UN-scaled density render_volume_density returns (model_helpers.py:86-97).  occl_reg_perc has no effect, here as in the
+// reference: compute_occl_loss ORs an all-ones back mask into the front mask unless use_back is passed and run_nerf.py never passes it,
+// so the term is the mean ray sum (losses.py:47-54 says the same).  sigma is f32 and dists f64: every sum runs in f64, as the reference's
+// dtype promotion has it.  One wave per ray, lanes strided over S; per-block partials -> one finishing block, all in fixed order (no
+// atomics: bit-identical run to run, and with or without the gradient outputs).
+// ------------------------------------------------------------------------------------------
+#define SLOSS_NPART 2
+__global__ __launch_bounds__(LOSS_NT) void nca_static_loss_rays(const NcaStaticLossArgs a) {
+    __shared__ double sh[LOSS_WAVES][SLOSS_NPART];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * LOSS_WAVES + wave;
+    double pixel = 0.0, occl = 0.0;
+    if (r < a.R) {
+        const float* sg = a.sigma + r * a.S;
+        float* gs = a.g_sigma ? a.g_sigma + r * a.S : nullptr;
+        const double gscale = a.w_occl * a.inv_R;
+        for (int s = lane; s < a.S; s += 64) {
+            const double dl = a.dists[s];
+            occl += (double)sg[s] * dl;
+            if (gs) gs[s] = (float)(gscale * dl);
+        }
+        occl = wsum(occl);
+        // pix: the caller's, or formed here from the forward's per-tile ray sums (same order as nca_pix_f32: bit-identical)
+        double pix_r;
+        if (a.ray_part) {
+            double sum = 0.0;
+            for (int c = 0; c < a.ray_nchunk; ++c) sum += a.ray_part[r * a.ray_nchunk + c];
+            pix_r = (double)a.ray_I0[r] - sum;
+            if (a.pix_out && lane == 0) a.pix_out[r] = pix_r;
+        } else pix_r = a.pix[r];
+        const double wr = a.wpix[r], diff = pix_r - a.gt[r];
+        if (a.g_pix && lane == 0) a.g_pix[r] = 2.0 * wr * diff * a.inv_R;
+        pixel = wr * diff * diff;
+    }
+    if (lane == 0) { sh[wave][0] = pixel; sh[wave][1] = occl; }
+    __syncthreads();
+    if (threadIdx.x < SLOSS_NPART) {
+        double s = 0.0;
+        for (int w = 0; w < LOSS_WAVES; ++w) s += sh[w][threadIdx.x];
+        a.partials[(int64_t)blockIdx.x * SLOSS_NPART + threadIdx.x] = s;
+    }
+}
+
+// One block of 1024 threads sums the per-block partials in a fixed order (thread t takes blocks t, t + 1024, ...; then the wave and the
+// 16 waves are folded in fixed trees) and assembles the four terms.
+__global__ __launch_bounds__(LOSS_FIN_NT) void nca_static_loss_finish(const NcaStaticLossArgs a, int nblocks) {
+    __shared__ double sh[LOSS_FIN_NT / 64][SLOSS_NPART];
+    double v[SLOSS_NPART] = {0.0, 0.0};
+    for (int b = threadIdx.x; b < nblocks; b += LOSS_FIN_NT) {
+        v[0] += a.partials[(int64_t)b * SLOSS_NPART];
+        v[1] += a.partials[(int64_t)b * SLOSS_NPART + 1];
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < SLOSS_NPART; ++k) {
+        const double x = wsum(v[k]);
+        if (lane == 0) sh[wave][k] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double res[SLOSS_NPART];
+#pragma unroll
+        for (int k = 0; k < SLOSS_NPART; ++k) {
+            double x = sh[0][k];
+            for (int w = 1; w < LOSS_FIN_NT / 64; ++w) x += sh[w][k];
+            res[k] = x;
+        }
+        double* t = a.terms;
+        t[NCA_ST_PIXEL] = res[0] * a.inv_R;
+        t[NCA_ST_OCCL] = res[1] * a.inv_R;
+        t[NCA_ST_LOSS] = t[NCA_ST_PIXEL] + a.w_occl * t[NCA_ST_OCCL];
+        t[3] = 0.0;
+        if (a.terms_f32)
+            for (int k = 0; k < NCA_ST_COUNT; ++k) a.terms_f32[k] = (float)t[k];
+    }
+}
+
+hipError_t nca_launch_static_loss(const NcaStaticLossArgs& a, hipStream_t st) {
+    const int nblocks = (int)((a.R + LOSS_WAVES - 1) / LOSS_WAVES);
+    hipLaunchKernelGGL(nca_static_loss_rays, dim3(nblocks), dim3(LOSS_NT), 0, st, a);
+    hipLaunchKernelGGL(nca_static_loss_finish, dim3(1), dim3(LOSS_FIN_NT), 0, st, a, nblocks);
+    return hipGetLastError();
+}
+
+int64_t nca_static_loss_partials_bytes(int64_t R) {
+    const int64_t nblocks = (R + LOSS_WAVES - 1) / LOSS_WAVES;
+    return nblocks * SLOSS_NPART * (int64_t)sizeof(double);
+}
+// <<< static-only loop
+
 // ------------------------------------------------------------------------------------------
 // stand-alone compositing of raw fields the caller already holds: render_volume_density_composite /
 // render_volume_density (train/model_helpers.py:72-97), one wave per ray, forward and backward

@@ -559,6 +559,60 @@ def fused_losses(pix, gt, wpix, sig_s, sig_d, dists, run_args, weights, inv_R=No
     return terms, g_pix, g_s, g_d
 
 
+# >>> static-only loop (run_nerf.py): not part of the composite f32 path, left out of f32_sources_sha (tools/psnr_cache.py)
+def static_losses(pix, gt, wpix, sigma, dists, w_occl, inv_R=None, want_grads=True, terms_f32: Optional[torch.Tensor] = None,
+                  pix_out: Optional[torch.Tensor] = None):
+    """weighted MSE + occl_weight * sum(compute_occl_loss(sigma, dists, occl_reg_perc)) of the static-only loop (train/run_nerf.py:227-230)
+    and their gradients in one HIP pass (nca_static_loss_fwd_bwd).
+
+    ``sigma`` f32[R,S] is the UN-scaled density of the single-field render; ``pix`` a tensor or the ``RaySums`` a single-field
+    ``render_forward_raw(..., want_pix=False)`` returned (the single-field forward leaves the same per-tile ray sums as the composite
+    one; ``pix_out`` f64[R] then receives pix).  ``w_occl`` = run_args.occl_weight_start, ``inv_R`` = 1 / global ray count (default
+    1/R).  Returns ``(terms f64[4] on device, g_pix f64[R] | None, g_sigma f32[R,S] | None)``; ``_capi.STATIC_TERM_NAMES`` names
+    the terms.  (occl_reg_perc is not an argument: it has no effect in the reference, see include/nerfca_hip.h.)"""
+    lib = _capi.lib()
+    _require_cuda(sigma, "sigma")
+    dev = sigma.device
+    if sigma.dim() != 2 or dists.dim() != 1 or dists.shape[0] != sigma.shape[1]:
+        raise _capi.NcaError(f"static_losses: expected sigma [R,S] and dists [S], got {tuple(sigma.shape)} and {tuple(dists.shape)}")
+    R, S = sigma.shape
+    f64 = lambda t: t.detach().to(device=dev, dtype=torch.float64).contiguous()
+    sums = pix if isinstance(pix, RaySums) else None
+    pix = None if sums is not None else f64(pix)
+    gt, wpix, dists = f64(gt), f64(wpix), f64(dists)
+    if gt.numel() != R or wpix.numel() != R or (pix is not None and pix.numel() != R):
+        raise _capi.NcaError(f"static_losses: pix, gt and wpix hold one value per ray ({R})")
+    sg = _f32c(sigma)
+    n_terms = len(_capi.STATIC_TERM_NAMES)
+    desc = _capi.NcaStaticLoss(R=R, S=S, reserved=0, w_occl=float(w_occl), inv_R=float(inv_R if inv_R is not None else 1.0 / R), terms_f32=None,
+                               ray_part=None, ray_I0=None, pix_out=None, ray_nchunk=0, reserved2=0)
+    if sums is not None:
+        if sums.part.numel() * sums.part.element_size() < R * sums.nchunk * 8 or sums.I0.shape[0] != R:
+            raise _capi.NcaError("RaySums does not belong to this batch")
+        desc.ray_part, desc.ray_I0, desc.ray_nchunk = ptr(sums.part), ptr(sums.I0), int(sums.nchunk)
+        if pix_out is not None:
+            if pix_out.dtype != torch.float64 or pix_out.numel() != R or not pix_out.is_contiguous() or pix_out.device != dev:
+                raise _capi.NcaError("pix_out must be a contiguous device f64[R]")
+            desc.pix_out = ptr(pix_out)
+    elif pix_out is not None:
+        raise _capi.NcaError("pix_out goes with a RaySums pix")
+    if terms_f32 is not None:
+        if terms_f32.dtype != torch.float32 or terms_f32.numel() != n_terms or not terms_f32.is_contiguous() or terms_f32.device != dev:
+            raise _capi.NcaError(f"terms_f32 must be a contiguous device f32[{n_terms}]")
+        desc.terms_f32 = ptr(terms_f32)
+    terms = torch.empty(n_terms, dtype=torch.float64, device=dev)
+    g_pix = g_sigma = None
+    if want_grads:
+        g_pix = torch.empty(R, dtype=torch.float64, device=dev)
+        g_sigma = torch.empty((R, S), dtype=torch.float32, device=dev)
+    wbytes = check(lib.nca_static_loss_workspace(R))
+    work = _scratch(wbytes, dev)
+    check(lib.nca_static_loss_fwd_bwd(C.byref(desc), ptr(pix), ptr(gt), ptr(wpix), ptr(sg), ptr(dists), ptr(terms), ptr(g_pix), ptr(g_sigma),
+                                      ptr(work), wbytes, _stream()))
+    return terms, g_pix, g_sigma
+# <<< static-only loop
+
+
 class _LossTermsFn(torch.autograd.Function):
     """compute_losses (train/model_helpers.py:250-262) as ONE autograd node over the HIP loss kernel: forward = the kernel's values,
     backward = the kernel in term-gradient mode (NcaLoss.term_grads: the eleven upstream scalars weight the terms' gradients), so a

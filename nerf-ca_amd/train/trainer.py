@@ -974,6 +974,212 @@ class StaticTrainer:
         self.sched.step()
         return loss.detach(), pixel.detach(), occl.detach()
 
+    # >>> static-only loop (run_nerf.py): not part of the composite f32 path, left out of f32_sources_sha (tools/psnr_cache.py)
+    # -- the same step without an autograd graph: HIP loss kernel, one flat gradient --------------
+    _phases_i64 = CompositeTrainer._phases_i64
+
+    def _fused_core(self, o, d, I0, gt, w, z, dists, inv_R: float, flat_out=None, terms_f32=None):
+        """Storing single-field forward -> nca_static_loss_fwd_bwd (values + d loss / d(pix, sigma)) -> fused backward.  The forward leaves
+        pix to the loss kernel (its per-tile ray sums: the single-field forward writes the same layout as the composite one), which stores
+        it; a net on the general kernels composites in a kernel of its own and hands over a tensor.  ``flat_out``: caller-owned f32 buffer the
+        gradient is written into.  Returns ``(terms f64[4], flat gradient f32, pix f64[R])``."""
+        from ..fused import RaySums, _RayBatch, render_backward_raw, render_forward_raw, static_losses
+        c = self.cfg
+        bs = self.s._binding
+        batch = _RayBatch(o, d, None, I0, z, dists, c.output_activation, True, 1e-2)
+        pix, sigma, _, keep = render_forward_raw(batch, bs, None, for_backward=True, want_pix=False)
+        pix_out = None
+        if isinstance(pix, RaySums):
+            pix_out = torch.empty(batch.R, dtype=torch.float64, device=sigma.device)
+        terms, g_pix, g_sigma = static_losses(pix, gt, w, sigma, dists, c.occl_weight_start, inv_R=inv_R, terms_f32=terms_f32, pix_out=pix_out)
+        flat, _ = render_backward_raw(batch, bs, None, keep, g_pix, g_sigma, None, out_s=flat_out)
+        return terms, flat, (pix_out if pix_out is not None else pix)
+
+    def fused_gradients_on(self, n_iter: int, origins, directions, I0, gt, w, t_rand, share: float = 1.0):
+        """``loss_on`` + ``backward`` of the fused path for callers that inject the batch and the jitter: what ``loss.backward()`` yields in
+        the reference (run_nerf.py:218-233) for one ray set, without an autograd graph and without touching the optimiser or the window
+        (``update_window`` first, as with ``loss_on``).  ``share`` = local / global ray count under sharding.  Returns ``(terms f64[4] =
+        [loss, pixel, occl, 0] (this ray set's share of the global values), flat gradient f32 in the binding's order
+        (``binding.split_grads``), pix)``; pix is f64 for f64 rays and f32 otherwise, as ``loss_on`` returns it."""
+        z = MH.randomize_depth(self.depth, self.device, t_rand)
+        dists = MH._interval_lengths(z, directions)
+        terms, flat, pix = self._fused_core(origins, directions, I0, gt, w, z, dists, inv_R=share / origins.shape[0])
+        if origins.dtype != torch.float64:
+            pix = pix.to(torch.float32)
+        return terms, flat, pix
+
+    def fused_gradients(self, n_iter: int):
+        """``fused_gradients_on`` for this rank's slice of the device-drawn global batch of iteration ``n_iter``: the ids, the jitter and the
+        slice bounds of ``step``.  The window is the caller's business (``step_fused`` updates it).  Returns ``(terms, flat gradient, pix)``."""
+        ids = self.draw_ray_ids_device(n_iter)
+        R = len(ids)
+        lo, hi = (R * self.rank) // self.world, (R * (self.rank + 1)) // self.world
+        rays = self.data.rays_train.index_select(0, ids[lo:hi])
+        return self.fused_gradients_on(n_iter, rays[:, 0, :], rays[:, 1, :], self.I0[: hi - lo], rays[:, 2, 0], rays[:, 3, 0],
+                                       self.draw_jitter(n_iter), share=(hi - lo) / R)
+
+    def step_fused(self, n_iter: int):
+        """``step`` without an autograd graph: window update -> fused forward -> HIP loss kernel -> fused backward -> (one all-reduce over
+        [flat gradient | the terms as f32]) -> Adam + LinearLR (torch's, the moments ``step`` uses).  Returns ``(loss, pixel, occl)`` like
+        ``step``; under sharding they are this rank's shares, which sum over the ranks."""
+        self.update_window(n_iter)
+        terms, flat, _ = self.fused_gradients(n_iter)
+        if self.world > 1:
+            both = torch.cat([flat, terms.to(torch.float32)])
+            dist.all_reduce(both, op=dist.ReduceOp.SUM)
+            flat = both[: flat.numel()]
+        for p, g in zip(self.s.parameters(), self.s._binding.split_grads(flat)):
+            p.grad = g
+        self.opt.step()
+        self.sched.step()
+        return terms[0], terms[1], terms[2]
+
+    # -- the same step as a replayed HIP graph --------------------------------------------------
+    def _draws_injected(self) -> bool:
+        """A test or a caller replaced the draw methods or the window update: the device-side draws of the graph step would not follow them.
+        (``CompositeTrainer._draws_injected`` cannot be borrowed: it names methods this class does not have.)"""
+        for name in ("draw_ray_ids_device", "draw_jitter", "update_window"):
+            if name in self.__dict__ or getattr(type(self), name) is not getattr(StaticTrainer, name):
+                return True
+        return False
+
+    def _device_window(self):
+        """The net's band window as the graph step keeps it: ``(NcaSchedules, device vector | None)``, or None where there is no device form.
+        free_windowed: the FreeNeRF mask made by nca_begin_step from the device's iteration counter (one NcaSchedules window, L <= 64);
+        encodings without a schedule keep a constant vector; nerfies_windowed eases with a host cosine and has no device form."""
+        from .. import _capi
+        c, m = self.cfg, self.s
+        sch = _capi.NcaSchedules()
+        sch.n_windows = 0
+        L = int(m.pos_enc_basis)
+        if c.static_pos_enc == "nerfies_windowed":
+            return None
+        if m._binding.net.enc_mode != _capi.ENC_BANDS or L <= 0:
+            return sch, None
+        if c.static_pos_enc == "free_windowed" and getattr(m, "use_pos_enc", None) == "free_windowed":
+            if L > 64:
+                return None
+            vec = torch.zeros(L, dtype=torch.float32, device=self.device)
+            sch.window[0].kind, sch.window[0].L, sch.window[0].window_start = _capi.WINDOW_FREE, L, int(m.pos_enc_window_start)
+            sch.window[0].decay_steps, sch.window[0].out = int(c.static_pos_enc_window_decay_steps), vec.data_ptr()
+            sch.n_windows = 1
+            return sch, vec
+        return sch, m._band_window().detach().to(device=self.device, dtype=torch.float32).contiguous().clone()
+
+    def _graph_route(self) -> bool:
+        """Does ``step_graph`` replay a graph (True) or route to ``step_fused`` (False)?  Whether the window has a device form is decided once;
+        the draw methods are looked at on every call, so one that is overridden after the capture is followed (by ``step_fused``) from then on."""
+        if getattr(self, "_graph_ok", None) is None:
+            on_cuda = torch.device(self.device).type == "cuda"
+            self._graph_ok = bool(on_cuda and self.world == 1 and self._device_window() is not None)
+        return self._graph_ok and not self._draws_injected()
+
+    def _graph_setup(self) -> None:
+        """Capture begin_step (ids, gather, jitter, FreeNeRF window) -> storing single-field forward -> static loss kernel -> backward into the
+        flat buffer -> library Adam + LinearLR, once: one linear chain of launches.  Everything a replay reads is owned by the trainer."""
+        from ..fused import FusedAdam, begin_step
+        c, dev = self.cfg, self.device
+        R = c.img_sample_size
+        bs = self.s._binding
+        self._sched, self._win_dev = self._device_window()
+        self._iter_dev = torch.zeros(1, dtype=torch.int64, device=dev)       # the iteration the next replay runs
+        self._bad_ids = torch.zeros(1, dtype=torch.int32, device=dev)        # ray ids outside the table that nca_begin_step clamped
+        self._graph_iter = None
+        if getattr(self.data, "phases_train", None) is None:                 # (a static data set may carry no phases: begin_step gathers one per ray)
+            self._phases64 = torch.zeros(self.data.rays_train.shape[0], dtype=torch.int64, device=dev)
+            phases = self._phases64
+        else:
+            phases = self._phases_i64()
+        self._graph_phases = phases
+        self.adam = FusedAdam([self.s], lr=c.lr, end_factor=c.lr_end_factor, total_iters=c.lr_decay_steps, iter_counter=self._iter_dev)
+        ns = bs.flat.numel()
+        self._flat = torch.zeros(ns + 4, dtype=torch.float32, device=dev)    # [flat gradient | the four terms as f32]
+        out = {}
+        sampler = self._sampler()
+
+        def body():
+            o, d, gt, w, _, z, dists = begin_step(sampler, 0, 0, R, self.data.rays_train, self._graph_phases, self.depth, iter_dev=self._iter_dev,
+                                                  schedules=self._sched, bad_ids=self._bad_ids)
+            terms, _, _ = self._fused_core(o, d, self.I0[:R], gt, w, z, dists, inv_R=1.0 / R, flat_out=self._flat[:ns], terms_f32=self._flat[ns:])
+            out["terms"] = terms
+            self.adam.step([self._flat[:ns]])
+
+        bs.static_window = self._win_dev
+        try:
+            saved = bs.flat.clone()
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):          # eager warm-up on the capture stream's allocator pool
+                body()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            bs.flat.copy_(saved)                   # undo the warm-up's optimiser step
+            for t in self.adam.exp_avg + self.adam.exp_avg_sq:
+                t.zero_()
+            self.adam._step.zero_()
+            self._iter_dev.zero_()
+            self._bad_ids.zero_()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                body()
+            self._graph = g
+        finally:
+            bs.static_window = None
+        self._graph_out = out
+
+    def step_graph(self, n_iter: int):
+        """``step_fused`` as ONE captured HIP graph -- begin_step (ids, gather, jitter and the FreeNeRF window made on the device from an
+        iteration counter), storing single-field forward, static loss kernel, backward, library Adam + LinearLR (which increments the
+        counter) -- replayed with no host work per step; a call that is not the successor of the previous one sets the counter first.  The
+        graph's Adam keeps its own moments: do not interleave with ``step`` / ``step_fused`` in one run.  The module's own window state is
+        not advanced per replay (``evaluate`` calls ``update_window`` itself).  Returns ``(loss, pixel, occl)``, overwritten by the next call.
+
+        Cases without a device form run ``step_fused`` instead (same step, launched from the host, torch Adam): ``nerfies_windowed`` (a host
+        cosine easing), more than 64 frequency bands, overridden ``draw_ray_ids_device`` / ``draw_jitter`` / ``update_window``, and
+        ``world > 1`` (a sharded static graph is out of scope)."""
+        if not self._graph_route():
+            return self.step_fused(n_iter)
+        if getattr(self, "_graph", None) is None:
+            self.update_window(n_iter)
+            self._graph_setup()
+        if self._graph_iter != n_iter:
+            self._iter_dev.fill_(n_iter)
+        self._graph_iter = n_iter + 1
+        self._graph.replay()
+        terms = self._graph_out["terms"]
+        return terms[0], terms[1], terms[2]
+
+    _bad_ids = None                # device i32[1] once a graph is captured: ray ids outside the table that nca_begin_step clamped
+    check_ray_ids = CompositeTrainer.check_ray_ids
+
+    # -- held-out view (run_nerf.py:254-291) -------------------------------------------------------
+    @torch.no_grad()
+    def evaluate(self, n_iter: int, chunk_rays: int = 65536):
+        """The display_every block of the reference: the single-field render of the held-out view with one fixed depth jitter drawn at first
+        use (run_nerf.py:128), the pixel loss with unit weights, the occlusion term and ``test_loss = pixel + occl_weight_start * occl``
+        from the HIP loss kernel (values only), ``test_psnr = -10 log10(test_loss)`` (:270-274).  Sets the window of iteration ``n_iter``
+        first, so a caller of ``step_graph`` (which does not advance the module's window state) cannot evaluate with a stale one."""
+        from ..fused import _RayBatch, render_forward_raw, static_losses
+        c, d, dev = self.cfg, self.data, self.device
+        self.update_window(n_iter)
+        self.check_ray_ids()
+        if getattr(self, "_test_jitter", None) is None:
+            self._test_jitter = torch.rand(self.depth.shape, generator=torch.Generator().manual_seed(self.seed * 7919 + 1))
+        z = MH.randomize_depth(self.depth, dev, self._test_jitter)
+        dists = MH._interval_lengths(z, d.test_directions)
+        bs = self.s._binding
+        pix, sigma = [], []
+        for i in range(0, d.test_origins.shape[0], chunk_rays):
+            o, dd = d.test_origins[i:i + chunk_rays], d.test_directions[i:i + chunk_rays]
+            I0 = torch.full((o.shape[0],), d.geo["max_pixel_value"], dtype=torch.float32, device=dev)
+            p, sg, _, _ = render_forward_raw(_RayBatch(o, dd, None, I0, z, dists, c.output_activation, True, 1e-2), bs, None)
+            pix.append(p); sigma.append(sg)
+        pix, sigma = torch.cat(pix), torch.cat(sigma)
+        gt = d.test_image.to(pix.dtype)
+        tk, _, _ = static_losses(pix, gt, torch.ones_like(gt), sigma, dists, c.occl_weight_start, inv_R=1.0 / pix.shape[0], want_grads=False)
+        return {"test_loss": tk[0], "test_psnr": -10.0 * torch.log10(tk[0]), "test_pixel_loss": tk[1], "test_occl_loss": tk[2], "pred": pix.float()}
+    # <<< static-only loop
+
 
 def MH_depth(geo, n, device):
     from .data_helpers import create_depth_values

@@ -11,7 +11,14 @@ Entry key: "<rays>x<samples>x<steps>|<variant>|<seed>" -> {"psnr_mse_db", "test_
 `f32_sources_sha` names the sources the runs were taken on -- EVERY kernel source and header of the library (the planner in nca_api.hip fixes
 the split counts, hence the summation order; the loss, Adam, sampler and compositing kernels are in other translation units than the f32
 fused kernels) and the Python that drives a run (trainer.py, fused.py, schedules.py, synthetic.py, psnr_run.py): comments and layout of the
-C sources are ignored.  A test run on other sources FAILS (tests/test_psnr_gates.py, tests/test_host_cpu.py): re-take the controls."""
+C sources are ignored.  A test run on other sources FAILS (tests/test_psnr_gates.py, tests/test_host_cpu.py): re-take the controls.
+
+One thing in those files is NOT hashed: the code of the static-only loop (train/run_nerf.py: StaticTrainer's fused steps, fused.static_losses,
+nca_static_loss_*), which sits in the same files between the marker comments `>>> static-only loop` and `<<< static-only loop`.  It renders one
+net with a loss of its own and is called by nothing on the composite path these controls were taken on (psnr_run.py drives CompositeTrainer), so
+adding or editing it leaves the f32 trajectory -- and this cache -- as it is.  Everything outside the markers is hashed as before; code that the
+composite path can reach does not belong between them.  (The gates also re-run two cached entries live per session, which a wrong marker could
+not survive.)"""
 import hashlib
 import json
 import os
@@ -28,12 +35,16 @@ def f32_source_list():
 OUT = os.path.join(ROOT, "tests", "golden", "psnr_f32_controls.json")
 
 
+# `// >>> static-only loop ...` up to the end of the line `// <<< static-only loop` (Python: `#`), markers included
+_UNHASHED = re.compile(r"[ \t]*(?://|#) >>> static-only loop.*?(?://|#) <<< static-only loop[^\n]*\n?", re.S)
+
+
 def f32_sources_sha():
     """Hash of the sources that determine the f32 trajectory (C sources: comment- and layout-insensitive; Python: whitespace-normalised)."""
     h = hashlib.sha256()
     for name in f32_source_list():
         path = os.path.join(ROOT, name) if "/" in name else os.path.join(CSRC, name)
-        text = open(path, encoding="utf-8", errors="replace").read()
+        text = _UNHASHED.sub("", open(path, encoding="utf-8", errors="replace").read())
         if not name.endswith(".py"):
             text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
             text = re.sub(r"//[^\n]*", " ", text)
