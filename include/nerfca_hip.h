@@ -532,6 +532,50 @@ int nca_timing_enable(int32_t on);
 int nca_timing_read(int32_t kind, double* total_ms, int64_t* launches);
 int nca_timing_reset(void);
 
+/* ---- view rendering: forward-only inference (export.render_view / render_sequence) --------
+ * Rays of ANY C-arm view generated on the device, the composition of two single-field renders into the composite / static / dynamic
+ * images of the reference's display block (train/run_composite.py:361, 405-413), and the per-image min / max normalisation it applies
+ * before logging.  The static field goes through the render forward above in single-field mode, once per view.  The dynamic field, once per
+ * (view, phase), does not (the render forward binds time latents to its second net only): it is the point forward on the chunk's query points,
+ * made by the query-point entry below, and the stand-alone compositing kernel in single-field mode.  Purely additive to ABI 13.  These entry points keep their OWN per-thread message: a negative return
+ * value is explained by the view-side accessor declared below, not by the library-wide one.  A refused call launches nothing. */
+
+/* One projection.  All f32: that is where train/proj_helpers.py:65-90 (get_ray_values_tigre) rounds. */
+typedef struct NcaView {
+    float pose[12];            /* rows of the 3x4 [R | t] of source_matrix_tigre([0,0,-DSO], theta, phi, larm), cast to f32 */
+    int32_t W, H;              /* nDetector */
+    float d_det[2], off_det[2], dsd;
+} NcaView;
+
+/* Origins and directions [n,3] of the pixels p = w*H + h in [p0, p0+n) (the order of the reference's flattened [W,H] images):
+ * u = (w + .5 - W/2) d_det[0] + off_det[0], v likewise from h, dir = R [u/dsd, v/dsd, 1] (not normalised), origin = t; every operation
+ * a rounded f32 one in the host function's order.  out_f64 = 1 writes the same f32 values widened to f64 (the ray table's type, for an
+ * f64 pix).  `view` is a host pointer.  NCA_E_INVALID: W or H <= 0, n <= 0, p0 < 0, p0 + n > W*H, a NULL pointer. */
+int nca_view_rays(const NcaView* view, int64_t p0, int64_t n, int32_t out_f64, void* origins, void* dirs, void* stream);
+
+/* Query points of a ray chunk: pts f32[R][S][3] = f32(o[r] + d[r] z[s]) as the fused render kernels form them from f64 rays [R,3] (summed
+ * in f64, rounded once); z is ONE depth vector f32[S].  The render forward binds time latents to its second
+ * net only, so a dynamic net alone cannot run there: it is evaluated on these points through the point forward, once per phase, and the
+ * stand-alone compositing kernel in single-field mode turns the raw field into its image.  NCA_E_INVALID: R or S <= 0, a NULL pointer. */
+int nca_view_points(int64_t R, int32_t S, const double* origins, const double* dirs, const float* z, float* pts, void* stream);
+
+/* pix_s, pix_d: the two single-field images [n] (f64 when pix_is_f64, else f32), each already I0 - sum(sigma dists scale).
+ * pred = f32((pix_s + pix_d) - i0), in f64 in exactly that order; pred_s = f32(pix_s); pred_d = f32(pix_d).
+ * pix_d == NULL (a static-only model): pred = pred_s and pred_d is filled with f32(i0). */
+int nca_view_compose(int64_t n, double i0, const void* pix_s, const void* pix_d, int32_t pix_is_f64, float* pred, float* pred_s,
+                     float* pred_d, void* stream);
+
+/* img [n_img][n] -> minmax [n_img][2] = (min, max) of each image and, when out != NULL, out [n_img][n] = (x - min) / (max - min) in f32
+ * (trainer.normalize_image; run_composite.py:405-413).  The one deliberate difference from that expression: a constant image
+ * (max == min) gives zeros, not NaN.  A NaN pixel makes min, max and the scaled image NaN, as torch.min / torch.max do there.  No atomics: per-block partials in `work`, one block per image folds them in a fixed order, then
+ * the scaling pass -- bit-identical run to run.  The workspace query returns the bytes ONE image of n pixels needs (a positive multiple of
+ * 256, non-decreasing in n; NCA_E_INVALID for n <= 0); a call needs n_img times that, else NCA_E_WORKSPACE. */
+int64_t nca_image_normalize_workspace(int64_t n);
+int nca_image_normalize(int32_t n_img, int64_t n, const float* img, float* out, float* minmax, void* work, int64_t work_bytes, void* stream);
+
+/* The message of the calling thread's last failed call of this section. */
+const char* nca_view_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

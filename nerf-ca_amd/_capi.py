@@ -122,6 +122,11 @@ class NcaPlan(C.Structure):
                [("wave_tiles", C.c_int64), ("overlap_cus", C.c_int32), ("overlap_forked", C.c_int32), ("reserved", C.c_int64 * 3)]
 
 
+class NcaView(C.Structure):
+    """One projection for nca_view_rays: the f32 3x4 [R | t] of source_matrix_tigre and the detector (include/nerfca_hip.h)."""
+    _fields_ = [("pose", C.c_float * 12), ("W", C.c_int32), ("H", C.c_int32), ("d_det", C.c_float * 2), ("off_det", C.c_float * 2), ("dsd", C.c_float)]
+
+
 class NcaError(RuntimeError):
     pass
 
@@ -180,6 +185,12 @@ SYMBOLS = {
     "nca_timing_enable": (C.c_int, [_I32]),
     "nca_timing_read": (C.c_int, [_I32, C.POINTER(C.c_double), C.POINTER(_I64)]),
     "nca_timing_reset": (C.c_int, []),
+    "nca_view_rays": (C.c_int, [C.POINTER(NcaView), _I64, _I64, _I32, _P, _P, _P]),
+    "nca_view_points": (C.c_int, [_I64, _I32, _P, _P, _P, _P, _P]),
+    "nca_view_compose": (C.c_int, [_I64, C.c_double, _P, _P, _I32, _P, _P, _P, _P]),
+    "nca_image_normalize_workspace": (_I64, [_I64]),
+    "nca_image_normalize": (C.c_int, [_I32, _I64, _P, _P, _P, _P, _I64, _P]),
+    "nca_view_last_error": (C.c_char_p, []),
 }
 
 
@@ -205,6 +216,13 @@ def check(rc: int) -> int:
     """Raise NcaError with the library's message when a call returned a negative code."""
     if rc < 0:
         raise NcaError(f"libnerfca_hip: {lib().nca_last_error().decode()} (code {rc})")
+    return rc
+
+
+def check_view(rc: int) -> int:
+    """``check`` for the view-rendering entry points (nca_view_*, nca_image_normalize*): they keep their own message."""
+    if rc < 0:
+        raise NcaError(f"libnerfca_hip: {lib().nca_view_last_error().decode()} (code {rc})")
     return rc
 
 
