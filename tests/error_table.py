@@ -4,7 +4,7 @@ import sys, os
 HERE = os.path.dirname(os.path.abspath(__file__)); ROOT = os.path.dirname(HERE); sys.path[:0] = [ROOT, HERE]
 import torch
 from oracle import nerfca_oracle as O
-from test_hip_parity import make_static, make_dynamic, _oracle_render_grads, grads_of
+from nca_testlib import make_static, make_dynamic, oracle_render_grads, grads_of, ray_inputs
 from conftest import rel_err
 from nerfca_amd import render_rays, set_precision
 dev = torch.device("cuda:0")
@@ -16,13 +16,9 @@ ss = O.NetSpec(num_filters=F, num_early_layers=2, num_time_dim=0, emulate_bf16=e
 sd = O.NetSpec(num_filters=F, num_early_layers=2, num_time_dim=8, emulate_bf16=emu)
 ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
 win = O.freq_mask_alpha(12, 75000, 150000, 1)[0]
-o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).double()
-d = (torch.rand(R, 3, generator=gen) - 0.5).double(); d = d / d.norm(dim=-1, keepdim=True)
-ph = torch.randint(0, 10, (R,), generator=gen)
-z = O.stratified_depths(O.depth_values(3.4259, 5.5741, S), torch.rand(S, generator=gen))
-I0 = torch.full((R,), 2.15991)
-cp, cs, cd = torch.randn(R, generator=gen).double(), torch.randn(R, S, generator=gen), torch.randn(R, S, generator=gen)
-pix, a, b, dists, ps32, pd32 = _oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, torch.float32)
+o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen, unit_dirs=False)
+d = d / d.norm(dim=-1, keepdim=True)
+pix, a, b, dists, ps32, pd32 = oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd)
 s = make_static(ps, dev, F=F, early=2, late=0); t = make_dynamic(pd, dev, F=F, early=2, late=0, T=8)
 set_precision(prec, s, t)
 s.update_freq_mask_alpha(75000, 150000); t.update_freq_mask_alpha(75000, 150000)

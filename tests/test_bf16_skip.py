@@ -11,18 +11,11 @@ import pytest
 import torch
 
 from conftest import nca_option, rel_err
+from nca_testlib import (BF_GRAD, BF_OUT, dev, grads_of, hip_render_grads, make_dynamic, make_static, oracle_render_grads, prefixed_grads,  # noqa: F401
+                         ray_inputs)
 from oracle import nerfca_oracle as O
-from test_fp8_stage import _oracle_grads
-from test_hip_parity import BF_GRAD, BF_OUT, grads_of, make_dynamic, make_static
-from test_recompute_bf16 import _hip_grads, _inputs
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
 
 
 @pytest.mark.parametrize("R,S,F,early,late,it", [(120, 50, 64, 2, 1, 150000), (64, 192, 128, 4, 2, 75000), (7, 500, 128, 1, 1, 150000), (40, 70, 32, 0, 3, 75000), (45, 64, 32, 1, 1, 150000),
@@ -36,11 +29,13 @@ def test_bf16_rays_with_a_skip_layer_vs_emulating_oracle(dev, R, S, F, early, la
     sd = O.NetSpec(num_filters=F, num_early_layers=max(early, 1), num_time_dim=8)
     ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
     win = O.freq_mask_alpha(12, it, 150000, 1)[0]
-    o, d, ph, z, I0, cp, cs, cd = _inputs(R, S, gen)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen)
     cp[: R // 4] = 0; cs[: R // 4] = 0; cd[: R // 4] = 0           # tiles whose upstream gradient is all zero
-    pix, a, b, dists, g8o = _oracle_grads(ps, ss, pd, sd, win, win, o, d, ph, I0, z, cp, cs, cd, False)                              # e5m2 / e4m3 staging
-    g16so = _oracle_grads(ps, ss, pd, sd, win, win, o, d, ph, I0, z, cp, cs, cd, False, formats=("bf16", "bf16"))[4]                # the bf16 store
-    g16o = _oracle_grads(ps, ss, pd, sd, win, win, o, d, ph, I0, z, cp, cs, cd, False, fp8=False, formats=None)[4]                   # no store: recompute
+    oracle = lambda **emu: oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, emulate=dict(emulate_bf16=True, **emu))  # noqa: E731
+    pix, a, b, dists, pso, pdo = oracle(emulate_fp8_stage=S)                                                            # e5m2 / e4m3 staging
+    g8o = prefixed_grads(pso, pdo)
+    g16so = prefixed_grads(*oracle(emulate_fp8_stage=S, emulate_stage_formats=("bf16", "bf16"))[4:])                    # the bf16 store
+    g16o = prefixed_grads(*oracle(emulate_stage_formats=None)[4:])                                                      # no store: recompute
     s = make_static(ps, dev, F=F, early=early, late=late)
     t = make_dynamic(pd, dev, F=F, early=max(early, 1), late=0, T=8)
     set_precision("bf16", s, t)
@@ -48,13 +43,13 @@ def test_bf16_rays_with_a_skip_layer_vs_emulating_oracle(dev, R, S, F, early, la
         m.update_freq_mask_alpha(it, 150000)
     saved = fused.BWD_WORKSPACE_BYTES
     try:
-        p8, a8, b8, g8 = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+        p8, a8, b8, g8 = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
         with nca_option("STAGE_FP8", 0):
-            p16s, a16s, b16s, g16s = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+            p16s, a16s, b16s, g16s = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
         with nca_option("STAGE_FP8", 0), nca_option("BF16_STORE", 0):
-            p16, a16, b16, g16 = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+            p16, a16, b16, g16 = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
         fused.BWD_WORKSPACE_BYTES = 24 << 20
-        pc, ac, bc, gc = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+        pc, ac, bc, gc = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
     finally:
         fused.BWD_WORKSPACE_BYTES = saved
     # the forward's arithmetic does not depend on the plan

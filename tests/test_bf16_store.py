@@ -11,28 +11,10 @@ import pytest
 import torch
 
 from conftest import rel_err
+from nca_testlib import BF_GRAD, BF_OUT, bf16_pair, dev, hip_render_grads, net_pair, oracle_render_grads, prefixed_grads, ray_inputs  # noqa: F401
 from oracle import nerfca_oracle as O
-from test_fp8_stage import _oracle_grads
-from test_hip_parity import BF_GRAD, BF_OUT, make_dynamic, make_static
-from test_recompute_bf16 import _hip_grads, _inputs
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def _models(dev, ps, pd, F, early, it_d):
-    from nerfca_amd import set_precision
-    s = make_static(ps, dev, F=F, early=early, late=0)
-    t = make_dynamic(pd, dev, F=F, early=early, late=0, T=8)
-    set_precision("bf16", s, t)
-    s.update_freq_mask_alpha(75000, 150000)
-    t.update_freq_mask_alpha(it_d, 150000)
-    return s, t
 
 
 @pytest.mark.parametrize("R,S,F,early", [(8, 16, 32, 1), (33, 50, 64, 3), (64, 192, 128, 4), (7, 500, 128, 4), (300, 70, 128, 2)])
@@ -44,14 +26,14 @@ def test_bf16_store_vs_emulating_oracle(dev, R, S, F, early, it_d):
     says "bf16 store, mode 5, nothing in 8 bits"."""
     from nerfca_amd import _capi, fused
     gen = torch.Generator().manual_seed(7300 + R + S)
-    ss = O.NetSpec(num_filters=F, num_early_layers=early, num_time_dim=0)
-    sd = O.NetSpec(num_filters=F, num_early_layers=early, num_time_dim=8)
-    ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
+    ss, sd, ps, pd = net_pair(F, early, gen)
     win, win_d = O.freq_mask_alpha(12, 75000, 150000, 1)[0], O.freq_mask_alpha(12, it_d, 150000, 1)[0]
-    o, d, ph, z, I0, cp, cs, cd = _inputs(R, S, gen)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen)
     cp[: R // 4] = 0; cs[: R // 4] = 0; cd[: R // 4] = 0           # tiles whose upstream gradient is all zero
-    pix, a, b, dists, go = _oracle_grads(ps, ss, pd, sd, win, win_d, o, d, ph, I0, z, cp, cs, cd, False, fp8=True, formats=("bf16", "bf16"))
-    s, t = _models(dev, ps, pd, F, early, it_d)
+    pix, a, b, dists, pso, pdo = oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, win_d=win_d,
+                                                     emulate=dict(emulate_bf16=True, emulate_fp8_stage=S, emulate_stage_formats=("bf16", "bf16")))
+    go = prefixed_grads(pso, pdo)
+    s, t = bf16_pair(dev, ps, pd, F, early, it_d)
     saved = fused.BWD_WORKSPACE_BYTES
     res, plans = {}, {}
     try:
@@ -59,7 +41,7 @@ def test_bf16_store_vs_emulating_oracle(dev, R, S, F, early, it_d):
                                ("store_resident", 6 << 30, {"stage_fp8": 0, "resident_min_tiles": 0}), ("store_chunks", 24 << 20, {"stage_fp8": 0, "resident_min_tiles": -1})):
             fused.BWD_WORKSPACE_BYTES = ws
             with fused.PlanScope(**opts) as sc:
-                res[name] = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+                res[name] = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
             plans[name] = sc.decided()
     finally:
         fused.BWD_WORKSPACE_BYTES = saved
@@ -87,16 +69,15 @@ def test_bf16_store_with_depth_gradients(dev, F, R, S):
     fragments) up to summation order; the parameter gradients agree to the bf16 tolerance."""
     from nerfca_amd import fused
     gen = torch.Generator().manual_seed(7400 + F)
-    ss, sd = O.NetSpec(num_filters=F, num_early_layers=2), O.NetSpec(num_filters=F, num_early_layers=2, num_time_dim=8)
-    s, t = _models(dev, O.init_params(ss, gen), O.init_params(sd, gen), F, 2, 10000)
+    s, t = bf16_pair(dev, *net_pair(F, 2, gen)[2:], F, 2, 10000)
     for m in (s, t):
         m.update_freq_mask_alpha(10000, 150000)
-    o, d, ph, z, I0, cp, cs, cd = _inputs(R, S, gen)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen)
     dists = O.ray_dists(z, torch.float64)
     res = {}
     for name, opts, mode in (("store", {"stage_fp8": 0}, 5), ("no_store", {"stage_fp8": 0, "bf16_store": 0}, 1)):
         with fused.PlanScope(**opts) as sc:
-            res[name] = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd, want_depth=True)
+            res[name] = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd, want_depth=True)
         assert sc.decided()["bwd_kernel_mode"] == mode, sc.decided()
     g1, g0 = res["store"][3], res["no_store"][3]
     assert float(g1["depth"].abs().max()) > 0 and rel_err(g1["depth"], g0["depth"]) < 2e-6

@@ -12,14 +12,9 @@ import torch
 
 import philox_ref as P
 from conftest import rel_err
+from nca_testlib import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
 
 
 def _tables(n_rays=5000, n_var=700, seed=0):

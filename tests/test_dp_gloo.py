@@ -6,7 +6,6 @@ implementation) and the process group is gloo.  Checked: the summed gradient and
 after Adam of a 2-rank step equal the 1-rank step on the same global batch.
 """
 import os
-import socket
 import sys
 
 import numpy as np
@@ -18,6 +17,8 @@ import torch.multiprocessing as mp
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from nca_testlib import free_port, oracle_fine_sampler  # noqa: E402
 
 
 def oracle_render(s, t, o, d, ph, I0, z, dists, act="softplus", single=False, scale=1e-2):
@@ -43,21 +44,6 @@ def oracle_render(s, t, o, d, ph, I0, z, dists, act="softplus", single=False, sc
     f = O.activation(act)
     a, b = f(raw_s[..., -1]) * scale, f(raw_d[..., -1]) * scale
     return I0 - ((a + b) * dists).sum(dim=-1), a, b
-
-
-def oracle_fine_sampler(sig_s, sig_d, z, u, reduce_max=None):
-    """fused.fine_depths signature with the oracle's arithmetic (model_helpers.py:131-148, 162-187)."""
-    from oracle import nerfca_oracle as O
-    R = sig_s.shape[0]
-    tsum = sig_s + sig_d
-    w = torch.cat([torch.full((R, 1), 1e-10), (tsum[:, 1:] - tsum[:, :-1]).abs()], -1)
-    wmax = w.max().reshape(1).clone()
-    if reduce_max is not None:
-        reduce_max(wmax)
-    w = w / wmax
-    zb = z[None, :].repeat(R, 1)
-    mid = 0.5 * (zb[:, 1:] + zb[:, :-1])
-    return torch.sort(torch.cat([O.sample_pdf(mid, w[:, 1:-1], u), zb], -1), -1)[0]
 
 
 def build(seed=0):
@@ -116,17 +102,11 @@ def _worker(rank, world, port, outdir, n_fine=0, depth_grads=False):
         dist.destroy_process_group()
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 @pytest.mark.timeout(300)
 def test_two_rank_step_equals_one_rank_step(tmp_path):
     torch.set_num_threads(2)
     g1, p1 = run_steps(0, 1)
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, free_port(), str(tmp_path)), nprocs=2, join=True)
     r0 = torch.load(tmp_path / "rank0.pt")
     r1 = torch.load(tmp_path / "rank1.pt")
     # every rank holds the same all-reduced gradient and the same parameters
@@ -150,7 +130,7 @@ def test_two_rank_step_with_fine_pass_equals_one_rank_step(tmp_path):
     torch.set_num_threads(2)
     g1, p1 = run_steps(0, 1, n_fine=6)
     assert g1.numel() == p1.numel() and float(g1.abs().max()) > 0
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path), 6), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, free_port(), str(tmp_path), 6), nprocs=2, join=True)
     r0 = torch.load(tmp_path / "rank0.pt")
     r1 = torch.load(tmp_path / "rank1.pt")
     assert torch.equal(r0["g"], r1["g"]) and torch.equal(r0["p"], r1["p"])
@@ -170,7 +150,7 @@ def test_two_rank_step_with_depth_gradients_equals_one_rank_step(tmp_path):
     g1, p1 = run_steps(0, 1, n_fine=6, depth_grads=True)
     g0, _ = run_steps(0, 1, n_fine=6, depth_grads=False)
     assert float((g1 - g0).abs().max() / g0.abs().max()) > 1e-2          # the through-depth term is there
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path), 6, True), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, free_port(), str(tmp_path), 6, True), nprocs=2, join=True)
     r0 = torch.load(tmp_path / "rank0.pt")
     r1 = torch.load(tmp_path / "rank1.pt")
     assert torch.equal(r0["g"], r1["g"]) and torch.equal(r0["p"], r1["p"])
@@ -255,7 +235,7 @@ def _stop_worker(rank, world, port, outdir):
 def test_early_stop_scalars_ride_on_the_gradient_all_reduce(tmp_path):
     """Under ray sharding a steady-state step issues ONE collective: the early-stop predicate's two scalars are appended to the
     flat gradient buffer instead of being all-reduced on their own (one all-reduce per step)."""
-    mp.spawn(_stop_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    mp.spawn(_stop_worker, args=(2, free_port(), str(tmp_path)), nprocs=2, join=True)
     for r in (0, 1):
         rec = torch.load(tmp_path / f"stop{r}.pt")
         assert rec["flag"] is False

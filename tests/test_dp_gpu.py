@@ -5,12 +5,13 @@ pass with the reference's through-depth gradient (cross-rank maximum and ray-0 b
 the same logic on the CPU with the oracle injected as the renderer; bench.py's N>1 path is this trainer over RCCL.
 """
 import os
-import socket
 
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
+
+from nca_testlib import free_port
 
 pytestmark = pytest.mark.gpu
 
@@ -73,12 +74,6 @@ def _worker(rank, world, port, outdir, mode, prec, backend="gloo"):
         dist.destroy_process_group()
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("mode,prec,gtol", [("fused", "f32", 1e-5), ("autograd", "f32", 1e-5), ("fused", "bf16", 1e-3), ("fine", "f32", 1e-3),
                                             ("graph", "f32", 1e-5), ("graph", "bf16", 1e-3), ("graphfine", "f32", 1e-3)])
@@ -88,7 +83,7 @@ def test_two_ranks_on_one_gpu_equal_one_rank(tmp_path, mode, prec, gtol):
     ill-conditioned: 1e-3).  Parameters after two steps only guard against a wrong step (Adam divides by sqrt(v))."""
     g1, p1 = _run(0, 1, mode, prec)
     assert float(g1.abs().max()) > 0
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path), mode, prec), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, free_port(), str(tmp_path), mode, prec), nprocs=2, join=True)
     r0 = torch.load(tmp_path / "rank0.pt")
     r1 = torch.load(tmp_path / "rank1.pt")
     assert torch.equal(r0["g"], r1["g"]) and torch.equal(r0["p"], r1["p"])
@@ -106,7 +101,7 @@ def test_two_ranks_over_rccl_equal_one_rank(tmp_path, mode, prec, gtol):
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs (RCCL takes one device per rank)")
     g1, p1 = _run(0, 1, mode, prec)
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path), mode, prec, "nccl"), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, free_port(), str(tmp_path), mode, prec, "nccl"), nprocs=2, join=True)
     r0 = torch.load(tmp_path / "rank0.pt")
     r1 = torch.load(tmp_path / "rank1.pt")
     assert torch.equal(r0["g"], r1["g"]) and torch.equal(r0["p"], r1["p"])
@@ -159,7 +154,7 @@ def test_one_rank_rccl_graph_step_is_bit_identical_to_no_process_group(tmp_path,
     driver's scaling run): the all-reduce between the two captured graphs must be a no-op on values -- ten steps, every loss and the
     final parameters bit-identical to the step without a process group."""
     l0, p0 = _graph_steps(10, prec, False)
-    mp.spawn(_rccl_one_rank_worker, args=(_free_port(), str(tmp_path), 10, prec), nprocs=1, join=True)
+    mp.spawn(_rccl_one_rank_worker, args=(free_port(), str(tmp_path), 10, prec), nprocs=1, join=True)
     r = torch.load(tmp_path / "rccl1.pt")
     assert torch.equal(r["l"], l0), (r["l"], l0)
     assert torch.equal(r["p"].view(torch.int32), p0.view(torch.int32))
@@ -185,7 +180,7 @@ def _bench(args, env_extra, timeout=900):
 def test_bench_over_rccl_with_one_rank():
     """bench.py's N > 1 code path on the one-GPU box: RCCL process group of one rank (NERFCA_FORCE_PG=1), gradient all-reduce
     every step, barriers, max-over-ranks time -- in a child process, as the driver runs it."""
-    port = str(_free_port())
+    port = str(free_port())
     line = _bench(["--gpus", "1", "--full", "--steps", "2", "--warmup", "1", "--rays", "8192", "--no-cpu-baseline", "--no-extras"],
                   {"NERFCA_FORCE_PG": "1", "RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": port})
     assert line["rccl_ranks"] == 1 and line["n_gpus"] == 1 and line["value"] > 0

@@ -12,46 +12,15 @@ within 1e-2 of the second -- although the staging itself moves a gradient of a f
 5 .. 25 % of its max-norm.  Outputs must be BIT-identical with and without the store (the forward's arithmetic does not change).  The training-quality gate (held-out PSNR within 0.1 dB of f32 at
 the bench configuration) is tests/test_psnr_gates.py, which runs the defaults (and both stagings at the reference's default batch).
 """
-import dataclasses
-
 import pytest
 import torch
 
 from conftest import nca_option, rel_err
+from nca_testlib import (BF_GRAD, BF_OUT, bf16_pair, count_launches, dev, hip_render_grads, make_dynamic, make_static, net_pair,  # noqa: F401
+                         oracle_render_grads, prefixed_grads, ray_inputs)
 from oracle import nerfca_oracle as O
-from test_hip_parity import BF_GRAD, BF_OUT, make_dynamic, make_static
-from test_recompute_bf16 import _hip_grads, _inputs, count_dgrad_launches
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def _oracle_grads(ps, ss, pd, sd, win, win_d, o, d, ph, I0, z, cp, cs, cd, onchip, fp8=True, ray_chunk=None, formats=("e5m2", "e4m3")):
-    R, S = o.shape[0], z.shape[0]
-    kw = dict(emulate_bf16=True, emulate_fp8_stage=S if fp8 else 0, emulate_onchip_last=onchip, emulate_stage_formats=formats)
-    sse, sde = dataclasses.replace(ss, **kw), dataclasses.replace(sd, **kw)
-    pso = {k: v.clone().requires_grad_(True) for k, v in ps.items()}
-    pdo = {k: v.clone().requires_grad_(True) for k, v in pd.items()}
-    outs = []
-    step = ray_chunk or R
-    for r0 in range(0, R, step):
-        sl = slice(r0, min(R, r0 + step))
-        n = sl.stop - sl.start
-        pts = O.query_points(o[sl], d[sl], z)
-        raw_s = O.static_forward(pso, sse, pts, win).reshape(n, S, -1)
-        raw_d = O.dynamic_forward(pdo, sde, pts, ph[sl][:, None].repeat(1, S).flatten(), win_d).reshape(n, S, -1)
-        pix, a, b, dists = O.composite(raw_s, raw_d, I0[sl], d[sl], z)
-        ((pix * cp[sl]).sum() + (a * cs[sl]).sum() * 50 + (b * cd[sl]).sum() * 50).backward()
-        outs.append((pix.detach(), a.detach(), b.detach()))
-    pix, a, b = (torch.cat([x[i] for x in outs]) for i in range(3))
-    g = {"s." + k: v.grad for k, v in pso.items()}
-    g.update({"t." + k: v.grad for k, v in pdo.items()})
-    return pix, a, b, dists, g
 
 
 @pytest.mark.parametrize("R,S,F,early", [(8, 16, 32, 1), (33, 50, 64, 3), (64, 192, 128, 4), (7, 500, 128, 4), (300, 70, 128, 2), (40, 130, 64, 0)])
@@ -62,31 +31,27 @@ def test_fp8_stage_vs_emulating_oracle(dev, R, S, F, early, it_d):
     the weight-gradient kernel) against the oracle that rounds what the kernels round; ragged tiles (S not a multiple of 64),
     nets without a hidden layer to stage (early = 0: no store, the recompute backward), one band window for both nets or one
     each; outputs bit-identical to the store-less plan; several ray chunks equal one."""
-    from nerfca_amd import fused, set_precision
-    onchip = False
+    from nerfca_amd import fused
     gen = torch.Generator().manual_seed(300 + R + S)
-    ss = O.NetSpec(num_filters=F, num_early_layers=early, num_time_dim=0)
-    sd = O.NetSpec(num_filters=F, num_early_layers=early, num_time_dim=8)
-    ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
+    ss, sd, ps, pd = net_pair(F, early, gen)
     win, win_d = O.freq_mask_alpha(12, 75000, 150000, 1)[0], O.freq_mask_alpha(12, it_d, 150000, 1)[0]
-    o, d, ph, z, I0, cp, cs, cd = _inputs(R, S, gen)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen)
     cp[: R // 4] = 0; cs[: R // 4] = 0; cd[: R // 4] = 0           # tiles whose upstream gradient is all zero
-    pix, a, b, dists, go = _oracle_grads(ps, ss, pd, sd, win, win_d, o, d, ph, I0, z, cp, cs, cd, onchip, fp8=early > 0)
-    go16 = _oracle_grads(ps, ss, pd, sd, win, win_d, o, d, ph, I0, z, cp, cs, cd, onchip, fp8=early > 0, formats=None)[4]
-    s = make_static(ps, dev, F=F, early=early, late=0)
-    t = make_dynamic(pd, dev, F=F, early=early, late=0, T=8)
-    set_precision("bf16", s, t)
-    s.update_freq_mask_alpha(75000, 150000)
-    t.update_freq_mask_alpha(it_d, 150000)
+    args = (ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd)
+    emu = dict(emulate_bf16=True, emulate_fp8_stage=S if early > 0 else 0)
+    pix, a, b, dists, pso, pdo = oracle_render_grads(*args, win_d=win_d, emulate=emu)
+    go = prefixed_grads(pso, pdo)
+    go16 = prefixed_grads(*oracle_render_grads(*args, win_d=win_d, emulate={**emu, "emulate_stage_formats": None})[4:])
+    s, t = bf16_pair(dev, ps, pd, F, early, it_d)
     saved = fused.BWD_WORKSPACE_BYTES
     launches = []
     try:
-        with count_dgrad_launches(launches):
-            p8, a8, b8, g8 = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+        with count_launches(launches, kinds=("bwd_dgrad",)):
+            p8, a8, b8, g8 = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
         with nca_option("STAGE_FP8", 0), nca_option("BF16_STORE", 0):          # no store: the recompute backward, nothing in 8 bits
-            p16, a16, b16, g16 = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+            p16, a16, b16, g16 = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
         fused.BWD_WORKSPACE_BYTES = 24 << 20
-        pc, ac, bc, gc = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+        pc, ac, bc, gc = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
     finally:
         fused.BWD_WORKSPACE_BYTES = saved
     if early > 0:
@@ -112,23 +77,17 @@ def test_fp8_stage_vs_emulating_oracle(dev, R, S, F, early, it_d):
 def test_fp8_stage_saturates_instead_of_overflowing(dev):
     """Upstream gradients and weights far outside any sane range: the conversions saturate (MODE.FP16_OVFL), nothing turns
     into inf / NaN on its way through the 8-bit blocks."""
-    from nerfca_amd import set_precision
     gen = torch.Generator().manual_seed(7)
     F, early, R, S = 64, 2, 12, 70
-    ss, sd = O.NetSpec(num_filters=F, num_early_layers=early), O.NetSpec(num_filters=F, num_early_layers=early, num_time_dim=8)
-    ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
+    ss, sd, ps, pd = net_pair(F, early, gen)
     for p in (ps, pd):
         for k in p:
             if k.endswith("weight") and "early_pts_layers" in k and not k.startswith("early_pts_layers.0."):
                 p[k] = p[k] * 1000.0           # activations ~1e5 (e4m3 x 4 tops out at 112), deltas amplified ~400x per layer (e5m2 at 57 344)
-    s = make_static(ps, dev, F=F, early=early, late=0)
-    t = make_dynamic(pd, dev, F=F, early=early, late=0, T=8)
-    set_precision("bf16", s, t)
-    for m in (s, t):
-        m.update_freq_mask_alpha(75000, 150000)
-    o, d, ph, z, I0, cp, cs, cd = _inputs(R, S, gen)
+    s, t = bf16_pair(dev, ps, pd, F, early, 75000)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen)
     dists = O.ray_dists(z, torch.float64)
-    _, _, _, g = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp * 1e20, cs * 1e20, cd * 1e20)
+    _, _, _, g = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp * 1e20, cs * 1e20, cd * 1e20)
     for k, v in g.items():
         assert bool(torch.isfinite(v).all()), k
     assert max(float(v.abs().max()) for v in g.values()) > 0
@@ -147,12 +106,12 @@ def test_fp8_stage_with_depth_gradients(dev):
     set_precision("bf16", s, t)
     for m in (s, t):
         m.update_freq_mask_alpha(10000, 150000)
-    o, d, ph, z, I0, cp, cs, cd = _inputs(R, S, gen)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen)
     dists = O.ray_dists(z, torch.float64)
-    _, _, _, gz = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd, want_depth=True)
+    _, _, _, gz = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd, want_depth=True)
     with nca_option("STAGE_FP8", 0), nca_option("BF16_STORE", 0):
-        _, _, _, gz16 = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd, want_depth=True)
-    _, _, _, g8 = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+        _, _, _, gz16 = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd, want_depth=True)
+    _, _, _, g8 = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
     assert rel_err(gz["depth"], gz16["depth"]) < 2e-6
     for k in g8:                                            # ~1 200 random-signed samples: the staging noise is 5 .. 25 % of a max-norm
         # (the output layer's weights: 1 170 terms g h that largely cancel, h as e4m3 -- 3 mantissa bits -- instead of bf16)

@@ -11,44 +11,13 @@ import pytest
 import torch
 
 from conftest import nca_option, rel_err
+from nca_testlib import (BF_GRAD, BF_OUT, bf16_pair, dev, grads_of, make_dynamic, make_static, model_def, net_pair, oracle_fine_sampler,  # noqa: F401
+                         oracle_render_grads, ray_inputs)
 from oracle import nerfca_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def model_def(F, early, late, pos_enc="free_windowed", L=12, T=0, gauss=None, sigma=2, device="cpu"):
-    d = dict(num_early_layers=early, num_late_layers=late, num_filters=F, num_input_channels=3, num_output_channels=1,
-             use_bias=True, pos_enc=pos_enc, pos_enc_window_start=1, pos_enc_basis=L, fourier_sigma=sigma,
-             fourier_gaussian=gauss, act_func="relu", device=device)
-    if T:
-        d.update(num_input_times=1, use_time_latents=True, num_time_dim=T)
-    return d
-
-
-def make_static(params, dev, **kw):
-    from nerfca_amd.model.CPPN import CPPN
-    m = CPPN(model_def(device=dev, **kw))
-    m.load_state_dict(params)
-    return m.to(dev)
-
-
-def make_dynamic(params, dev, **kw):
-    from nerfca_amd.model.Temporal import Temporal
-    m = Temporal(model_def(device=dev, **kw))
-    m.load_state_dict(params)
-    return m.to(dev)
-
-
-def grads_of(model):
-    return {k: p.grad.detach().cpu() for k, p in model.named_parameters()}
 
 
 # ------------------------------------------------------------------------------------------
@@ -135,20 +104,6 @@ def test_render_forward_vs_reference(golden, dev, R, S, dtn):
     assert all(v is None for v in res[4:])
 
 
-def _oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, dt, win_d=None):
-    """Outputs and all parameter gradients of the oracle evaluated in dtype `dt` (same f32 query points)."""
-    S = z.shape[0]
-    pso = {k: v.clone().to(dt).requires_grad_(True) for k, v in ps.items()}
-    pdo = {k: v.clone().to(dt).requires_grad_(True) for k, v in pd.items()}
-    pts = O.query_points(o, d, z).to(dt)
-    w = win.to(dt)
-    raw_s = O.static_forward(pso, ss, pts, w).reshape(o.shape[0], S, -1)
-    raw_d = O.dynamic_forward(pdo, sd, pts, ph[:, None].repeat(1, S).flatten(), w if win_d is None else win_d.to(dt)).reshape(o.shape[0], S, -1)
-    pix, a, b, dists = O.composite(raw_s, raw_d, I0.to(dt), d, z.to(dt))
-    ((pix * cp).sum() + (a * cs).sum() * 50 + (b * cd).sum() * 50).backward()
-    return pix, a, b, dists, pso, pdo
-
-
 @pytest.mark.parametrize("R,S,F", [(8, 16, 32), (33, 50, 64), (64, 192, 128), (7, 500, 128)])
 @pytest.mark.parametrize("f64", [True, False])
 def test_render_backward_vs_oracle(dev, R, S, F, f64):
@@ -160,21 +115,12 @@ def test_render_backward_vs_oracle(dev, R, S, F, f64):
     its measured rounding noise on the same inputs is the meaningful floor."""
     from nerfca_amd import render_rays
     gen = torch.Generator().manual_seed(1234 + R + S)
-    ss = O.NetSpec(num_filters=F, num_early_layers=3, num_time_dim=0)
-    sd = O.NetSpec(num_filters=F, num_early_layers=3, num_time_dim=8)
-    ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
+    ss, sd, ps, pd = net_pair(F, 3, gen)
     win = O.freq_mask_alpha(12, 75000, 150000, 1)[0]
-    dt = torch.float64 if f64 else torch.float32
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).to(dt)
-    d = (torch.rand(R, 3, generator=gen) - 0.5).to(dt)
-    d = d / d.norm(dim=-1, keepdim=True) * 1.001
-    ph = torch.randint(0, 10, (R,), generator=gen)
-    z = O.stratified_depths(O.depth_values(3.4259, 5.5741, S), torch.rand(S, generator=gen))
-    I0 = torch.full((R,), 2.15991)
-    cp, cs, cd = torch.randn(R, generator=gen).to(dt), torch.randn(R, S, generator=gen), torch.randn(R, S, generator=gen)
-
-    pix, a, b, dists, ps32, pd32 = _oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, torch.float32)
-    _, _, _, _, ps64, pd64 = _oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, torch.float64)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen, dtype=torch.float64 if f64 else torch.float32)
+    args = (ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd)
+    pix, a, b, dists, ps32, pd32 = oracle_render_grads(*args, dt=torch.float32)
+    _, _, _, _, ps64, pd64 = oracle_render_grads(*args, dt=torch.float64)
 
     s = make_static(ps, dev, F=F, early=3, late=0)
     t = make_dynamic(pd, dev, F=F, early=3, late=0, T=8)
@@ -235,21 +181,17 @@ def test_backward_is_linear_in_upstream_gradient(dev):
     calls -- so grads(g1 + g2) == grads(g1) + grads(g2) up to f32 summation rounding."""
     from nerfca_amd import render_rays
     gen = torch.Generator().manual_seed(11)
-    ss, sd = O.NetSpec(num_filters=128), O.NetSpec(num_filters=128, num_time_dim=8)
-    s = make_static(O.init_params(ss, gen), dev, F=128, early=4, late=0)
-    t = make_dynamic(O.init_params(sd, gen), dev, F=128, early=4, late=0, T=8)
+    ss, sd, ps, pd = net_pair(128, 4, gen)
+    s = make_static(ps, dev, F=128, early=4, late=0)
+    t = make_dynamic(pd, dev, F=128, early=4, late=0, T=8)
     for m in (s, t):
         m.update_freq_mask_alpha(75000, 150000)
     R, S = 2048, 192
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).double().to(dev)
-    d = (torch.rand(R, 3, generator=gen) - 0.5).double().to(dev)
-    ph = torch.randint(0, 10, (R,), generator=gen).to(dev)
-    z = O.stratified_depths(O.depth_values(3.4259, 5.5741, S), torch.rand(S, generator=gen))
+    o, d, ph, z, I0, *c0 = ray_inputs(R, S, gen, unit_dirs=False)
+    c1 = (torch.randn(R, generator=gen).double(), torch.randn(R, S, generator=gen), torch.randn(R, S, generator=gen))
     dists = O.ray_dists(z, torch.float64).to(dev)
-    z = z.to(dev)
-    I0 = torch.full((R,), 2.15991, device=dev)
-    coef = [(torch.randn(R, generator=gen).double().to(dev), torch.randn(R, S, generator=gen).to(dev), torch.randn(R, S, generator=gen).to(dev))
-            for _ in range(2)]
+    o, d, ph, z, I0 = (x.to(dev) for x in (o, d, ph, z, I0))
+    coef = [tuple(x.to(dev) for x in c) for c in (c0, c1)]
     coef.append(tuple(a + b for a, b in zip(*coef)))
     flat = []
     for cp, cs, cd in coef:
@@ -273,8 +215,6 @@ def test_backward_is_linear_in_upstream_gradient(dev):
 # blocks that only the weight-gradient kernel reads cross HBM as e4m3 (layer inputs) / e5m2 (output gradients, one power-of-two
 # scale per 64-sample tile).  The oracle emulates that too (NetSpec.emulate_fp8_stage = samples per ray), so the bound stays.
 # ------------------------------------------------------------------------------------------
-BF_OUT, BF_GRAD = 2e-3, 5e-2
-
 
 @pytest.mark.parametrize("F,early", [(32, 0), (32, 4), (64, 4), (128, 0), (128, 4)])
 def test_bf16_points_vs_emulating_oracle(golden, dev, F, early):
@@ -308,37 +248,19 @@ def test_bf16_points_vs_emulating_oracle(golden, dev, F, early):
         assert rel_err(gd[k], pdo[k].grad) < BF_GRAD, ("dynamic", k)
 
 
-def _oracle_render_grads_bf16(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, win_d=None, fp8=True, onchip=False):
-    import dataclasses
-    kw = dict(emulate_bf16=True, emulate_fp8_stage=z.shape[0] if fp8 else 0, emulate_onchip_last=onchip)
-    return _oracle_render_grads(ps, dataclasses.replace(ss, **kw), pd, dataclasses.replace(sd, **kw),
-                                win, o, d, ph, I0, z, cp, cs, cd, torch.float32, win_d=win_d)
-
-
 @pytest.mark.parametrize("R,S,F", [(8, 16, 32), (33, 50, 64), (64, 192, 128), (7, 500, 128)])
 @pytest.mark.parametrize("it_d", [75000, 30000])
 def test_bf16_render_vs_emulating_oracle(dev, R, S, F, it_d):
     """it_d == 75000: both nets use the same band window (the composite.txt default); 30000: a different window per net."""
-    from nerfca_amd import render_rays, set_precision
+    from nerfca_amd import render_rays
     gen = torch.Generator().manual_seed(4321 + R + S)
-    ss = O.NetSpec(num_filters=F, num_early_layers=3, num_time_dim=0)
-    sd = O.NetSpec(num_filters=F, num_early_layers=3, num_time_dim=8)
-    ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
+    ss, sd, ps, pd = net_pair(F, 3, gen)
     win = O.freq_mask_alpha(12, 75000, 150000, 1)[0]
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).double()
-    d = (torch.rand(R, 3, generator=gen) - 0.5).double()
-    d = d / d.norm(dim=-1, keepdim=True) * 1.001
-    ph = torch.randint(0, 10, (R,), generator=gen)
-    z = O.stratified_depths(O.depth_values(3.4259, 5.5741, S), torch.rand(S, generator=gen))
-    I0 = torch.full((R,), 2.15991)
-    cp, cs, cd = torch.randn(R, generator=gen).double(), torch.randn(R, S, generator=gen), torch.randn(R, S, generator=gen)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen)
     win_d = O.freq_mask_alpha(12, it_d, 150000, 1)[0]
-    pix, a, b, dists, pse, pde = _oracle_render_grads_bf16(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, win_d=win_d)
-    s = make_static(ps, dev, F=F, early=3, late=0)
-    t = make_dynamic(pd, dev, F=F, early=3, late=0, T=8)
-    set_precision("bf16", s, t)
-    s.update_freq_mask_alpha(75000, 150000)
-    t.update_freq_mask_alpha(it_d, 150000)
+    pix, a, b, dists, pse, pde = oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, win_d=win_d,
+                                                     emulate=dict(emulate_bf16=True, emulate_fp8_stage=S))
+    s, t = bf16_pair(dev, ps, pd, F, 3, it_d)
     pix2, a2, b2 = render_rays(s, t, o.to(dev), d.to(dev), ph.to(dev), I0.to(dev), z.to(dev), dists.to(dev))
     assert pix2.dtype == torch.float64 and tuple(a2.shape) == (R, S)
     assert rel_err(a2.cpu(), a) < BF_OUT and rel_err(b2.cpu(), b) < BF_OUT
@@ -350,14 +272,9 @@ def test_bf16_render_vs_emulating_oracle(dev, R, S, F, it_d):
 
 
 def test_bf16_backward_is_deterministic(dev):
-    from nerfca_amd import render_rays, set_precision
+    from nerfca_amd import render_rays
     gen = torch.Generator().manual_seed(5)
-    ss, sd = O.NetSpec(num_filters=128), O.NetSpec(num_filters=128, num_time_dim=8)
-    s = make_static(O.init_params(ss, gen), dev, F=128, early=4, late=0)
-    t = make_dynamic(O.init_params(sd, gen), dev, F=128, early=4, late=0, T=8)
-    set_precision("bf16", s, t)
-    for m in (s, t):
-        m.update_freq_mask_alpha(75000, 150000)
+    s, t = bf16_pair(dev, *net_pair(128, 4, gen)[2:], 128, 4, 75000)
     R, S = 300, 192
     o = (torch.rand(R, 3, generator=gen) + 2).double().to(dev)
     d = (torch.rand(R, 3, generator=gen) - 0.5).double().to(dev)
@@ -669,7 +586,6 @@ def test_trainer_with_fine_pass_vs_oracle(dev):
     from nerfca_amd.model.CPPN import CPPN
     from nerfca_amd.model.Temporal import Temporal
     from nerfca_amd.train.trainer import CompositeTrainer, TrainConfig
-    from tests.test_dp_gloo import oracle_fine_sampler
     S, NF, R, n_iter = 24, 8, 96, 2000
     data = synthetic.make_dataset(16, S, dev, views=synthetic.TRAIN_VIEWS[:2], n_phases=3, F=32)
     cfg = TrainConfig(depth_samples_per_ray_coarse=S, depth_samples_per_ray_fine=NF, img_sample_size=R, favor_s_weight_delay_steps=0,
@@ -992,12 +908,8 @@ def test_depth_gradient_vs_oracle(golden, dev, enc, F, ray_dt):
             m.update_windowed_alpha(30000, 100000)
         win = O.nerfies_window(L, O.windowed_alpha(L, 30000, 100000))
     R, S = 7, 45
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).to(ray_dt)
-    d = (torch.rand(R, 3, generator=gen) - 0.5).to(ray_dt)
-    ph = torch.randint(0, 10, (R,), generator=gen)
-    z_all = torch.sort(3.4259 + (5.5741 - 3.4259) * torch.rand(R, S, generator=gen), -1)[0]
-    I0 = torch.full((R,), 2.15991)
-    cp, cs, cd = torch.randn(R, generator=gen).double(), torch.randn(R, S, generator=gen), torch.randn(R, S, generator=gen)
+    o, d, ph, z_all, I0, cp, cs, cd = ray_inputs(R, S, gen, dtype=ray_dt, unit_dirs=False, z="per_ray")
+    cp = cp.double()
 
     def tail(z0, like):
         return torch.cat((z0[1:] - z0[:-1], torch.tensor([1e-10], dtype=like.dtype, device=z0.device)), -1)
@@ -1046,19 +958,13 @@ def test_depth_gradient_shared_depth_vector(dev):
     summed over the rays; against autograd through the f64 oracle."""
     from nerfca_amd import render_rays
     gen = torch.Generator().manual_seed(4321)
-    ss, sd = O.NetSpec(num_filters=64, num_early_layers=2), O.NetSpec(num_filters=64, num_early_layers=2, num_time_dim=8)
-    ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
+    ss, sd, ps, pd = net_pair(64, 2, gen)
     s, t = make_static(ps, dev, F=64, early=2, late=0), make_dynamic(pd, dev, F=64, early=2, late=0, T=8)
     for m in (s, t):
         m.update_freq_mask_alpha(60000, 150000)
     win = O.freq_mask_alpha(12, 60000, 150000, 1)[0]
     R, S = 11, 50
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).double()
-    d = (torch.rand(R, 3, generator=gen) - 0.5).double()
-    ph = torch.randint(0, 10, (R,), generator=gen)
-    z = O.stratified_depths(O.depth_values(3.4259, 5.5741, S), torch.rand(S, generator=gen))
-    I0 = torch.full((R,), 2.15991)
-    cp, cs, cd = torch.randn(R, generator=gen).double(), torch.randn(R, S, generator=gen), torch.randn(R, S, generator=gen)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen, unit_dirs=False)
 
     def oracle(dt):
         pso = {k: v.clone().to(dt) for k, v in ps.items()}
@@ -1091,17 +997,12 @@ def test_depth_gradient_bf16_vs_f32(dev, F, R, S, it_s, it_d, tol):
     with a parity claim."""
     from nerfca_amd import fused, render_rays, set_precision
     gen = torch.Generator().manual_seed(5 + F)
-    ss, sd = O.NetSpec(num_filters=F, num_early_layers=3), O.NetSpec(num_filters=F, num_early_layers=3, num_time_dim=8)
-    s = make_static(O.init_params(ss, gen), dev, F=F, early=3, late=0)
-    t = make_dynamic(O.init_params(sd, gen), dev, F=F, early=3, late=0, T=8)
+    ss, sd, ps, pd = net_pair(F, 3, gen)
+    s = make_static(ps, dev, F=F, early=3, late=0)
+    t = make_dynamic(pd, dev, F=F, early=3, late=0, T=8)
     s.update_freq_mask_alpha(it_s, 150000)
     t.update_freq_mask_alpha(it_d, 150000)
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).double().to(dev)
-    d = (torch.rand(R, 3, generator=gen) - 0.5).double().to(dev)
-    ph = torch.randint(0, 10, (R,), generator=gen).to(dev)
-    z_all = torch.sort(3.4259 + (5.5741 - 3.4259) * torch.rand(R, S, generator=gen), -1)[0].to(dev)
-    I0 = torch.full((R,), 2.15991, device=dev)
-    cp, cs, cd = torch.randn(R, generator=gen).double().to(dev), torch.randn(R, S, generator=gen).to(dev), torch.randn(R, S, generator=gen).to(dev)
+    o, d, ph, z_all, I0, cp, cs, cd = (x.to(dev) for x in ray_inputs(R, S, gen, unit_dirs=False, z="per_ray"))
 
     def run():
         zt = z_all.clone().requires_grad_(True)
@@ -1207,18 +1108,13 @@ def test_depth_gradient_store_recompute_and_chunks(dev, limit, ws):
     chunk or in many (a 1 MiB workspace: one ray per chunk) -- each against the default run (store, one chunk)."""
     from nerfca_amd import fused, render_rays
     gen = torch.Generator().manual_seed(99)
-    ss, sd = O.NetSpec(num_filters=64, num_early_layers=2), O.NetSpec(num_filters=64, num_early_layers=2, num_time_dim=8)
-    s = make_static(O.init_params(ss, gen), dev, F=64, early=2, late=0)
-    t = make_dynamic(O.init_params(sd, gen), dev, F=64, early=2, late=0, T=8)
+    ss, sd, ps, pd = net_pair(64, 2, gen)
+    s = make_static(ps, dev, F=64, early=2, late=0)
+    t = make_dynamic(pd, dev, F=64, early=2, late=0, T=8)
     for m in (s, t):
         m.update_freq_mask_alpha(60000, 150000)
     R, S = 19, 70
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).double().to(dev)
-    d = (torch.rand(R, 3, generator=gen) - 0.5).double().to(dev)
-    ph = torch.randint(0, 10, (R,), generator=gen).to(dev)
-    z_all = torch.sort(3.4259 + (5.5741 - 3.4259) * torch.rand(R, S, generator=gen), -1)[0].to(dev)
-    I0 = torch.full((R,), 2.15991, device=dev)
-    cp, cs, cd = torch.randn(R, generator=gen).double().to(dev), torch.randn(R, S, generator=gen).to(dev), torch.randn(R, S, generator=gen).to(dev)
+    o, d, ph, z_all, I0, cp, cs, cd = (x.to(dev) for x in ray_inputs(R, S, gen, unit_dirs=False, z="per_ray"))
 
     def run():
         for m in (s, t):
@@ -1245,7 +1141,6 @@ def test_depth_gradient_store_recompute_and_chunks(dev, limit, ws):
 def test_nets_of_different_width(dev, prec):
     """static_num_filters != temp_num_filters: per-net fused launches + compositing kernel; outputs and all
     gradients against the oracle (bf16: the emulating oracle)."""
-    import dataclasses
     from nerfca_amd import render_rays, set_precision
     gen = torch.Generator().manual_seed(77)
     emu = prec == "bf16"
@@ -1254,13 +1149,8 @@ def test_nets_of_different_width(dev, prec):
     ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
     win = O.freq_mask_alpha(12, 75000, 150000, 1)[0]
     R, S = 21, 80
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).double()
-    d = (torch.rand(R, 3, generator=gen) - 0.5).double()
-    ph = torch.randint(0, 10, (R,), generator=gen)
-    z = O.stratified_depths(O.depth_values(3.4259, 5.5741, S), torch.rand(S, generator=gen))
-    I0 = torch.full((R,), 2.15991)
-    cp, cs, cd = torch.randn(R, generator=gen).double(), torch.randn(R, S, generator=gen), torch.randn(R, S, generator=gen)
-    pix, a, b, dists, pso, pdo = _oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, torch.float32)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen, unit_dirs=False)
+    pix, a, b, dists, pso, pdo = oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd)
     s = make_static(ps, dev, F=64, early=2, late=0)
     t = make_dynamic(pd, dev, F=128, early=3, late=0, T=8)
     set_precision(prec, s, t)
@@ -1280,7 +1170,6 @@ def test_nets_of_different_width(dev, prec):
 @pytest.mark.parametrize("R,S", [(1, 1), (1, 2), (3, 1), (1, 65), (2, 1000), (129, 33)])
 def test_degenerate_and_ragged_sizes(dev, prec, R, S):
     """Single ray / single sample / one sample past a tile / S far above a tile, forward and backward."""
-    import dataclasses
     from nerfca_amd import render_rays, set_precision
     gen = torch.Generator().manual_seed(100 * R + S)
     emu = prec == "bf16"
@@ -1289,13 +1178,9 @@ def test_degenerate_and_ragged_sizes(dev, prec, R, S):
     sd = O.NetSpec(num_filters=32, num_early_layers=1, num_time_dim=8, emulate_bf16=emu, emulate_fp8_stage=S if emu else 0)
     ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
     win = O.freq_mask_alpha(12, 75000, 150000, 1)[0]
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).double()
-    d = (torch.rand(R, 3, generator=gen) - 0.5).double()
-    ph = torch.randint(0, 10, (R,), generator=gen)
+    o, d, ph, _, I0, cp, cs, cd = ray_inputs(R, S, gen, unit_dirs=False, z=None)
     z = O.depth_values(3.4259, 5.5741, S) if S > 1 else torch.tensor([4.0])
-    I0 = torch.full((R,), 2.15991)
-    cp, cs, cd = torch.randn(R, generator=gen).double(), torch.randn(R, S, generator=gen), torch.randn(R, S, generator=gen)
-    pix, a, b, dists, pso, pdo = _oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, torch.float32)
+    pix, a, b, dists, pso, pdo = oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd)
     s = make_static(ps, dev, F=32, early=1, late=0)
     t = make_dynamic(pd, dev, F=32, early=1, late=0, T=8)
     set_precision(prec, s, t)
@@ -1640,21 +1525,15 @@ def test_stored_forward_backward_equals_recompute(dev, prec, it_d, R, S, F, earl
     backward: tests/test_fp8_stage.py and tests/test_recompute_bf16.py pin each against the oracle that rounds what it rounds.)"""
     from nerfca_amd import fused, render_rays, set_precision
     gen = torch.Generator().manual_seed(77 + R)
-    ss = O.NetSpec(num_filters=F, num_early_layers=early, num_time_dim=0)
-    sd = O.NetSpec(num_filters=F, num_early_layers=early, num_time_dim=8)
-    s = make_static(O.init_params(ss, gen), dev, F=F, early=early, late=0)
-    t = make_dynamic(O.init_params(sd, gen), dev, F=F, early=early, late=0, T=8)
+    ss, sd, ps, pd = net_pair(F, early, gen)
+    s = make_static(ps, dev, F=F, early=early, late=0)
+    t = make_dynamic(pd, dev, F=F, early=early, late=0, T=8)
     set_precision(prec, s, t)
     s.update_freq_mask_alpha(75000, 150000)
     t.update_freq_mask_alpha(it_d, 150000)
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).double().to(dev)
-    d = (torch.rand(R, 3, generator=gen) - 0.5).double().to(dev)
-    ph = torch.randint(0, 10, (R,), generator=gen).to(dev)
-    z = O.stratified_depths(O.depth_values(3.4259, 5.5741, S), torch.rand(S, generator=gen))
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen, unit_dirs=False)
     dists = O.ray_dists(z, torch.float64).to(dev)
-    z = z.to(dev)
-    I0 = torch.full((R,), 2.15991, device=dev)
-    cp, cs, cd = torch.randn(R, generator=gen).double().to(dev), torch.randn(R, S, generator=gen).to(dev), torch.randn(R, S, generator=gen).to(dev)
+    o, d, ph, z, I0, cp, cs, cd = (x.to(dev) for x in (o, d, ph, z, I0, cp, cs, cd))
     outs = []
     saved = fused.STORE_FORWARD_LIMIT_BYTES, fused.BWD_WORKSPACE_BYTES
     try:
@@ -1726,21 +1605,13 @@ def test_fused_step_over_ray_micro_batches(dev, prec, graph):
 def test_no_forward_store_without_autograd(dev):
     """Under torch.no_grad() (evaluation) the autograd entry point must not ask the forward for a store: same outputs,
     and no store-sized allocation."""
-    from nerfca_amd import fused, render_rays, set_precision
+    from nerfca_amd import fused, render_rays
     gen = torch.Generator().manual_seed(3)
-    ss, sd = O.NetSpec(num_filters=64, num_early_layers=2), O.NetSpec(num_filters=64, num_early_layers=2, num_time_dim=8)
-    s = make_static(O.init_params(ss, gen), dev, F=64, early=2, late=0)
-    t = make_dynamic(O.init_params(sd, gen), dev, F=64, early=2, late=0, T=8)
-    set_precision("bf16", s, t)
-    for m in (s, t):
-        m.update_freq_mask_alpha(75000, 150000)
+    s, t = bf16_pair(dev, *net_pair(64, 2, gen)[2:], 64, 2, 75000)
     R, S = 256, 64
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).double().to(dev)
-    d = (torch.rand(R, 3, generator=gen) - 0.5).double().to(dev)
-    ph = torch.randint(0, 10, (R,), generator=gen).to(dev)
-    z = O.stratified_depths(O.depth_values(3.4259, 5.5741, S), torch.rand(S, generator=gen))
+    o, d, ph, z, I0 = ray_inputs(R, S, gen, unit_dirs=False)[:5]
     dists = O.ray_dists(z, torch.float64).to(dev)
-    I0 = torch.full((R,), 2.15991, device=dev)
+    o, d, ph, I0 = (x.to(dev) for x in (o, d, ph, I0))
     calls = []
     orig = fused.render_forward_raw
     fused.render_forward_raw = lambda *a, **k: (calls.append(k.get("for_backward", False)), orig(*a, **k))[1]
@@ -1769,13 +1640,8 @@ def test_f32_store_with_skip_layers(dev, late):
     for m in (s, t):
         m.update_freq_mask_alpha(75000, 150000)
     win = O.freq_mask_alpha(12, 75000, 150000, 1)[0]
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).double()
-    d = (torch.rand(R, 3, generator=gen) - 0.5).double()
-    ph = torch.randint(0, 10, (R,), generator=gen)
-    z = O.stratified_depths(O.depth_values(3.4259, 5.5741, S), torch.rand(S, generator=gen))
-    I0 = torch.full((R,), 2.15991)
-    cp, cs, cd = torch.randn(R, generator=gen).double(), torch.randn(R, S, generator=gen), torch.randn(R, S, generator=gen)
-    pix, a, b, dists, pso, pdo = _oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, torch.float32)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen, unit_dirs=False)
+    pix, a, b, dists, pso, pdo = oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd)
     outs = []
     saved = fused.STORE_FORWARD_LIMIT_BYTES
     try:
@@ -1834,22 +1700,14 @@ def test_nets_without_biases(dev, prec):
     from nerfca_amd.model.Temporal import Temporal
     R, S, F = 33, 50, 64
     gen = torch.Generator().manual_seed(77)
-    ss = O.NetSpec(num_filters=F, num_early_layers=3, num_time_dim=0)
-    sd = O.NetSpec(num_filters=F, num_early_layers=3, num_time_dim=8)
-    ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
+    ss, sd, ps, pd = net_pair(F, 3, gen)
     for prm in (ps, pd):
         for k in prm:
             if k.endswith(".bias"):
                 prm[k] = torch.zeros_like(prm[k])
     win = O.freq_mask_alpha(12, 75000, 150000, 1)[0]
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).to(torch.float64)
-    d = (torch.rand(R, 3, generator=gen) - 0.5).to(torch.float64)
-    d = d / d.norm(dim=-1, keepdim=True) * 1.001
-    ph = torch.randint(0, 10, (R,), generator=gen)
-    z = O.stratified_depths(O.depth_values(3.4259, 5.5741, S), torch.rand(S, generator=gen))
-    I0 = torch.full((R,), 2.15991)
-    cp, cs, cd = torch.randn(R, generator=gen).to(torch.float64), torch.randn(R, S, generator=gen), torch.randn(R, S, generator=gen)
-    pix, a, b, dists, ps64, pd64 = _oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, torch.float64)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen)
+    pix, a, b, dists, ps64, pd64 = oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, dt=torch.float64)
 
     ds, dd = model_def(F=F, early=3, late=0, device=dev), model_def(F=F, early=3, late=0, T=8, device=dev)
     ds["use_bias"] = dd["use_bias"] = False
@@ -1908,15 +1766,10 @@ def test_nets_of_any_width_up_to_128(dev, Fs, Fd, late):
     sd = O.NetSpec(num_filters=Fd, num_early_layers=3, num_time_dim=8)
     ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
     win = O.freq_mask_alpha(12, 75000, 150000, 1)[0]
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).to(torch.float64)
-    d = (torch.rand(R, 3, generator=gen) - 0.5).to(torch.float64)
-    d = d / d.norm(dim=-1, keepdim=True) * 1.001
-    ph = torch.randint(0, 10, (R,), generator=gen)
-    z = O.stratified_depths(O.depth_values(3.4259, 5.5741, S), torch.rand(S, generator=gen))
-    I0 = torch.full((R,), 2.15991)
-    cp, cs, cd = torch.randn(R, generator=gen).to(torch.float64), torch.randn(R, S, generator=gen), torch.randn(R, S, generator=gen)
-    pix, a, b, dists, ps64, pd64 = _oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, torch.float64)
-    _, _, _, _, ps32, pd32 = _oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, torch.float32)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen)
+    args = (ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd)
+    pix, a, b, dists, ps64, pd64 = oracle_render_grads(*args, dt=torch.float64)
+    _, _, _, _, ps32, pd32 = oracle_render_grads(*args, dt=torch.float32)
     s = make_static(ps, dev, F=Fs, early=2, late=late)
     t = make_dynamic(pd, dev, F=Fd, early=3, late=0, T=8)
     s.update_freq_mask_alpha(75000, 150000)

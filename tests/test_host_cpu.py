@@ -13,15 +13,7 @@ import pytest
 import torch
 
 from conftest import ROOT, rel_err
-
-
-def model_def(F=128, early=4, late=0, pos_enc="free_windowed", L=12, T=0, gauss=None):
-    d = dict(num_early_layers=early, num_late_layers=late, num_filters=F, num_input_channels=3, num_output_channels=1,
-             use_bias=True, pos_enc=pos_enc, pos_enc_window_start=1, pos_enc_basis=L, fourier_sigma=2,
-             fourier_gaussian=gauss, act_func="relu", device="cpu")
-    if T:
-        d.update(num_input_times=1, use_time_latents=True, num_time_dim=T)
-    return d
+from nca_testlib import model_def
 
 
 # ----------------------------------------------------------------------------- C ABI surface

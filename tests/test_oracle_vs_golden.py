@@ -8,14 +8,10 @@ import pytest
 import torch
 
 from conftest import rel_err
+from nca_testlib import spec_from
 from oracle import nerfca_oracle as O
 
 torch.set_num_threads(4)
-
-
-def spec_from(F, early, late, pos_enc="free_windowed", L=12, T=0, start=1, coef=None):
-    return O.NetSpec(num_filters=F, num_early_layers=early, num_late_layers=late, pos_enc=pos_enc, pos_enc_basis=L,
-                     pos_enc_window_start=start, num_time_dim=T, fourier_coefficients=coef)
 
 
 # ------------------------------------------------------------------------------- (1) pos-enc

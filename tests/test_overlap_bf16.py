@@ -13,24 +13,17 @@ import pytest
 import torch
 
 from conftest import nca_option
+from nca_testlib import bf16_pair, dev, hip_render_grads, net_pair, ray_inputs  # noqa: F401
 from oracle import nerfca_oracle as O
-from test_recompute_bf16 import _hip_grads, _inputs
-from test_resident_bf16 import _nets
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
 
 
 def _run(dev, s, t, inputs, dists, ovl, scope_opts=None):
     from nerfca_amd import fused
     o, d, ph, z, I0, cp, cs, cd = inputs
     with fused.PlanScope(resident_min_tiles=0, overlap_cus=ovl, **(scope_opts or {})) as sc:
-        out = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+        out = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
     torch.cuda.synchronize()
     return out, sc.decided()
 
@@ -38,8 +31,8 @@ def _run(dev, s, t, inputs, dists, ovl, scope_opts=None):
 @pytest.mark.parametrize("R,S", [(1024, 192), (700, 500)])
 def test_overlapped_backward_equals_plain_backward(dev, R, S):
     gen = torch.Generator().manual_seed(5100 + R)
-    s, t = _nets(dev, 128, 4, 75000, gen)
-    inputs = _inputs(R, S, gen)
+    s, t = bf16_pair(dev, *net_pair(128, 4, gen)[2:], 128, 4, 75000)
+    inputs = ray_inputs(R, S, gen)
     o, d, ph, z, I0 = inputs[:5]
     dists = O.composite(torch.zeros(R, S, 1), torch.zeros(R, S, 1), I0, d, z)[3]
     cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -63,8 +56,8 @@ def test_overlapped_backward_over_several_ray_chunks(dev):
     from nerfca_amd import fused
     R, S = 2048, 192
     gen = torch.Generator().manual_seed(5200)
-    s, t = _nets(dev, 128, 4, 75000, gen)
-    inputs = _inputs(R, S, gen)
+    s, t = bf16_pair(dev, *net_pair(128, 4, gen)[2:], 128, 4, 75000)
+    inputs = ray_inputs(R, S, gen)
     o, d, ph, z, I0 = inputs[:5]
     dists = O.composite(torch.zeros(R, S, 1), torch.zeros(R, S, 1), I0, d, z)[3]
     saved = fused.BWD_WORKSPACE_BYTES
@@ -86,8 +79,8 @@ def test_small_batches_and_other_paths_do_not_fork(dev):
     """Below the size the overlapped plan is for (and on every path but mode 5 with resident images) the option changes nothing."""
     R, S = 64, 192
     gen = torch.Generator().manual_seed(5300)
-    s, t = _nets(dev, 128, 4, 75000, gen)
-    inputs = _inputs(R, S, gen)
+    s, t = bf16_pair(dev, *net_pair(128, 4, gen)[2:], 128, 4, 75000)
+    inputs = ray_inputs(R, S, gen)
     o, d, ph, z, I0 = inputs[:5]
     dists = O.composite(torch.zeros(R, S, 1), torch.zeros(R, S, 1), I0, d, z)[3]
     base, p0 = _run(dev, s, t, inputs, dists, 0)

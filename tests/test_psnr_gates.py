@@ -60,17 +60,13 @@ from types import SimpleNamespace
 import pytest
 import torch
 
+from nca_testlib import dev  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ("psnr_mse_db", "test_psnr_reference_def_db")
 CONTROLS = ("f32_bf16init", "f32_kick2e-3", "f32_kick4e-3")
 STRICT_DB, BRANCH_DB, STABLE_DB = 0.05, 0.1, 0.05          # (a seed whose f32 spread is in (0.05, 0.1] is gated at 0.1: `strict_gate`)
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
 
 
 def _load(name):

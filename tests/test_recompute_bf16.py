@@ -7,85 +7,14 @@ round 4 (never better in held-out PSNR than the 8-bit staged stor
 per-caller planner options that replaced "set a process-wide option, run, set it back": `fused.PlanScope` (NcaRays.plan_opts /
 plan_out, ABI 9).
 """
-import contextlib
-import dataclasses
-
 import pytest
 import torch
 
 from conftest import rel_err
+from nca_testlib import BF_GRAD, BF_OUT, bf16_pair, dev, hip_render_grads, make_dynamic, make_static, net_pair, oracle_render_grads, ray_inputs  # noqa: F401
 from oracle import nerfca_oracle as O
-from test_hip_parity import BF_GRAD, BF_OUT, make_dynamic, make_static
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-@contextlib.contextmanager
-def count_dgrad_launches(out):
-    from nerfca_amd import _capi
-    _capi.timing_reset()
-    _capi.timing_enable(True)
-    try:
-        yield
-    finally:
-        out.append(_capi.timing_read("bwd_dgrad")[1])
-        _capi.timing_enable(False)
-        _capi.timing_reset()
-
-
-def _inputs(R, S, gen):
-    o = (torch.rand(R, 3, generator=gen) * 0.2 + torch.tensor([3.0, -2.0, 2.5])).double()
-    d = (torch.rand(R, 3, generator=gen) - 0.5).double()
-    d = d / d.norm(dim=-1, keepdim=True) * 1.001
-    ph = torch.randint(0, 10, (R,), generator=gen)
-    z = O.stratified_depths(O.depth_values(3.4259, 5.5741, S), torch.rand(S, generator=gen))
-    I0 = torch.full((R,), 2.15991)
-    cp, cs, cd = torch.randn(R, generator=gen).double(), torch.randn(R, S, generator=gen), torch.randn(R, S, generator=gen)
-    return o, d, ph, z, I0, cp, cs, cd
-
-
-def _oracle_grads_bf16(ps, ss, pd, sd, win, win_d, o, d, ph, I0, z, cp, cs, cd, ray_chunk=None):
-    """Outputs and parameter gradients of the bf16-emulating oracle; rays are independent, so the backward may run
-    over ray chunks (bounded memory) and add up."""
-    R, S = o.shape[0], z.shape[0]
-    sse, sde = dataclasses.replace(ss, emulate_bf16=True), dataclasses.replace(sd, emulate_bf16=True)
-    pso = {k: v.clone().requires_grad_(True) for k, v in ps.items()}
-    pdo = {k: v.clone().requires_grad_(True) for k, v in pd.items()}
-    outs = []
-    step = ray_chunk or R
-    for r0 in range(0, R, step):
-        sl = slice(r0, min(R, r0 + step))
-        n = sl.stop - sl.start
-        pts = O.query_points(o[sl], d[sl], z)
-        raw_s = O.static_forward(pso, sse, pts, win).reshape(n, S, -1)
-        raw_d = O.dynamic_forward(pdo, sde, pts, ph[sl][:, None].repeat(1, S).flatten(), win_d).reshape(n, S, -1)
-        pix, a, b, dists = O.composite(raw_s, raw_d, I0[sl], d[sl], z)
-        ((pix * cp[sl]).sum() + (a * cs[sl]).sum() * 50 + (b * cd[sl]).sum() * 50).backward()
-        outs.append((pix.detach(), a.detach(), b.detach()))
-    pix, a, b = (torch.cat([x[i] for x in outs]) for i in range(3))
-    return pix, a, b, dists, pso, pdo
-
-
-def _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd, want_depth=False):
-    from nerfca_amd import render_rays
-    for m in (s, t):
-        m.zero_grad()
-    zz = z.to(dev)
-    if want_depth:
-        zz = zz[None, :].repeat(o.shape[0], 1).clone().requires_grad_(True)
-    pix, a, b = render_rays(s, t, o.to(dev), d.to(dev), ph.to(dev), I0.to(dev), zz, dists.to(dev))
-    ((pix * cp.to(dev)).sum() + (a * cs.to(dev)).sum() * 50 + (b * cd.to(dev)).sum() * 50).backward()
-    g = {"s." + k: p.grad.detach().clone() for k, p in s.named_parameters()}
-    g.update({"t." + k: p.grad.detach().clone() for k, p in t.named_parameters()})
-    if want_depth:
-        g["depth"] = zz.grad.detach().clone()
-    return pix.detach(), a.detach(), b.detach(), g
 
 
 @pytest.mark.parametrize("R,S,F,early", [(8, 16, 32, 1), (33, 50, 64, 3), (64, 192, 128, 4), (7, 500, 128, 4), (300, 70, 128, 2)])
@@ -95,26 +24,20 @@ def test_no_store_recompute_backward_vs_emulating_oracle(dev, R, S, F, early, it
     gradient is within the bf16 tolerance of the oracle that rounds what the kernels round, with one ray chunk and with several;
     the forward's outputs are bit-identical to those of the default plan (the 8-bit staged store changes nothing the forward
     returns).  it_d == 75000: one band window for both nets; 30000: one per net."""
-    from nerfca_amd import _capi, fused, set_precision
+    from nerfca_amd import _capi, fused
     gen = torch.Generator().manual_seed(900 + R + S)
-    ss = O.NetSpec(num_filters=F, num_early_layers=early, num_time_dim=0)
-    sd = O.NetSpec(num_filters=F, num_early_layers=early, num_time_dim=8)
-    ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
+    ss, sd, ps, pd = net_pair(F, early, gen)
     win, win_d = O.freq_mask_alpha(12, 75000, 150000, 1)[0], O.freq_mask_alpha(12, it_d, 150000, 1)[0]
-    o, d, ph, z, I0, cp, cs, cd = _inputs(R, S, gen)
-    pix, a, b, dists, pse, pde = _oracle_grads_bf16(ps, ss, pd, sd, win, win_d, o, d, ph, I0, z, cp, cs, cd)
-    s = make_static(ps, dev, F=F, early=early, late=0)
-    t = make_dynamic(pd, dev, F=F, early=early, late=0, T=8)
-    set_precision("bf16", s, t)
-    s.update_freq_mask_alpha(75000, 150000)
-    t.update_freq_mask_alpha(it_d, 150000)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen)
+    pix, a, b, dists, pse, pde = oracle_render_grads(ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd, win_d=win_d, emulate={"emulate_bf16": True})
+    s, t = bf16_pair(dev, ps, pd, F, early, it_d)
     saved = fused.BWD_WORKSPACE_BYTES
     res, plans = {}, {}
     try:
         for name, ws, opts in (("default", 6 << 30, {}), ("no_store", 6 << 30, {"stage_fp8": 0, "bf16_store": 0}), ("no_store_chunks", 24 << 20, {"stage_fp8": 0, "bf16_store": 0})):
             fused.BWD_WORKSPACE_BYTES = ws
             with fused.PlanScope(**opts) as sc:
-                res[name] = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+                res[name] = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
             plans[name] = sc.decided()
     finally:
         fused.BWD_WORKSPACE_BYTES = saved
@@ -147,12 +70,12 @@ def test_no_store_with_depth_gradients(dev, F, R, S):
     set_precision("bf16", s, t)
     for m in (s, t):
         m.update_freq_mask_alpha(10000, 150000)
-    o, d, ph, z, I0, cp, cs, cd = _inputs(R, S, gen)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen)
     dists = O.ray_dists(z, torch.float64)
     res = {}
     for name, opts in (("default", {}), ("no_store", {"stage_fp8": 0, "bf16_store": 0})):
         with fused.PlanScope(**opts) as sc:
-            res[name] = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd, want_depth=True)
+            res[name] = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd, want_depth=True)
         assert sc.decided()["bwd_kernel_mode"] == (5 if name == "default" else 1), sc.decided()
     g1, g0 = res["no_store"][3], res["default"][3]
     assert float(g1["depth"].abs().max()) > 0
@@ -198,23 +121,18 @@ def test_two_trainers_keep_their_own_planner_options(dev):
 
 
 def test_plan_options_are_validated_and_the_retired_store_format_is_refused(dev):
-    from nerfca_amd import _capi, fused, set_precision
+    from nerfca_amd import _capi, fused
     with pytest.raises(_capi.NcaError):
         _capi.NcaPlanOpts(onchip_min_tiles=0)          # the retired option has no per-call field either
     with pytest.raises(_capi.NcaError):
         _capi.get_option(0)                            # NCA_OPT_RESERVED0
     gen = torch.Generator().manual_seed(3)
-    ss, sd = O.NetSpec(num_filters=32, num_early_layers=1), O.NetSpec(num_filters=32, num_early_layers=1, num_time_dim=8)
-    s = make_static(O.init_params(ss, gen), dev, F=32, early=1, late=0)
-    t = make_dynamic(O.init_params(sd, gen), dev, F=32, early=1, late=0, T=8)
-    set_precision("bf16", s, t)
-    for m in (s, t):
-        m.update_freq_mask_alpha(75000, 150000)
-    o, d, ph, z, I0, cp, cs, cd = _inputs(8, 16, gen)
+    s, t = bf16_pair(dev, *net_pair(32, 1, gen)[2:], 32, 1, 75000)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(8, 16, gen)
     dists = O.ray_dists(z, torch.float64)
     with fused.PlanScope(stage_fp8=7):          # not 0 / 1 / -1
         with pytest.raises(_capi.NcaError, match="NCA_OPT_STAGE_FP8"):
-            _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+            hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
     # a backward that is told "format 2" (the bf16-staged store of ABI <= 8) is refused
     batch = fused._RayBatch(o.to(dev), d.to(dev), ph.to(dev), I0.to(dev), z.to(dev), dists.to(dev), "softplus", False, 1e-2)
     pix, a, b, keep = fused.render_forward_raw(batch, s._binding, t._binding, for_backward=True)

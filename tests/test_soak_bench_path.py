@@ -18,18 +18,11 @@ import pytest
 import torch
 
 from conftest import nca_option, rel_err
+from nca_testlib import (BF_GRAD, BF_OUT, bf16_pair, dev, hip_render_grads, make_dynamic, make_static, net_pair, oracle_render_grads,  # noqa: F401
+                         prefixed_grads, ray_inputs)
 from oracle import nerfca_oracle as O
-from test_fp8_stage import _oracle_grads
-from test_hip_parity import BF_GRAD, BF_OUT, make_dynamic, make_static
-from test_recompute_bf16 import _hip_grads, _inputs
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
 
 
 def _trainer(dev, prec, rays, samples, data):
@@ -195,14 +188,15 @@ def test_fuzz_resident_equals_streaming_and_oracle(dev, R, S, F, early, it_s, it
     bits, and both sit within the bf16 bounds of the oracle that rounds what the kernels round."""
     from nerfca_amd import set_precision
     gen = torch.Generator().manual_seed(7000 + 31 * R + S + F + early)
-    ss = O.NetSpec(num_filters=F, num_early_layers=early, num_time_dim=0)
-    sd = O.NetSpec(num_filters=F, num_early_layers=early, num_time_dim=8)
-    ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
+    ss, sd, ps, pd = net_pair(F, early, gen)
     win, win_d = O.freq_mask_alpha(12, it_s, 150000, 1)[0], O.freq_mask_alpha(12, it_d, 150000, 1)[0]
-    o, d, ph, z, I0, cp, cs, cd = _inputs(R, S, gen)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen)
     staged = early > 0 and bool(fp8)
-    pix, a, b, dists, go = _oracle_grads(ps, ss, pd, sd, win, win_d, o, d, ph, I0, z, cp, cs, cd, False, fp8=staged)
-    go16 = go if not staged else _oracle_grads(ps, ss, pd, sd, win, win_d, o, d, ph, I0, z, cp, cs, cd, False, fp8=staged, formats=None)[4]
+    args = (ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd)
+    emu = dict(emulate_bf16=True, emulate_fp8_stage=S if staged else 0)
+    pix, a, b, dists, pso, pdo = oracle_render_grads(*args, win_d=win_d, emulate=emu)
+    go = prefixed_grads(pso, pdo)
+    go16 = go if not staged else prefixed_grads(*oracle_render_grads(*args, win_d=win_d, emulate={**emu, "emulate_stage_formats": None})[4:])
     s = make_static(ps, dev, F=F, early=early, late=0)
     t = make_dynamic(pd, dev, F=F, early=early, late=0, T=8)
     set_precision("bf16", s, t)
@@ -211,11 +205,11 @@ def test_fuzz_resident_equals_streaming_and_oracle(dev, R, S, F, early, it_s, it
     got = {}
     for name, thr in (("streaming", -1), ("resident", 0)):
         with nca_option("RESIDENT_MIN_TILES", thr), nca_option("STAGE_FP8", fp8), nca_option("BF16_STORE", 0):
-            got[name] = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+            got[name] = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
     g16 = got["streaming"][3]
     if staged:
         with nca_option("RESIDENT_MIN_TILES", -1), nca_option("STAGE_FP8", 0), nca_option("BF16_STORE", 0):
-            g16 = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)[3]
+            g16 = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)[3]
     for i in range(3):
         assert torch.equal(got["resident"][i], got["streaming"][i]), i
     assert rel_err(got["resident"][1].cpu(), a) < BF_OUT and rel_err(got["resident"][2].cpu(), b) < BF_OUT
@@ -233,28 +227,25 @@ def test_fp8_stage_at_natural_resident_threshold_vs_oracle(dev):
     """(iv) the planner's own plan at the smallest batch that runs the resident kernels on this part (8 * 8 * CUs wave tiles:
     5 504 rays x 192 samples on 256 CUs), default nets, fp8 staging: every gradient against the oracle that stages in fp8 (run
     over ray chunks on the host cores), and bit-equal to the streaming kernels on the same batch."""
-    from nerfca_amd import _capi, set_precision
+    from nerfca_amd import _capi
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     S = 192
     R = (8 * 8 * cus + 2) // 3 + 40
     assert _capi.get_option(_capi.OPT_RESIDENT_MIN_TILES) == 8 * 8 * cus
     gen = torch.Generator().manual_seed(4343)
-    ss, sd = O.NetSpec(num_filters=128), O.NetSpec(num_filters=128, num_time_dim=8)
-    ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
+    ss, sd, ps, pd = net_pair(128, 4, gen)
     win = O.freq_mask_alpha(12, 75000, 150000, 1)[0]
-    o, d, ph, z, I0, cp, cs, cd = _inputs(R, S, gen)
-    pix, a, b, dists, go = _oracle_grads(ps, ss, pd, sd, win, win, o, d, ph, I0, z, cp, cs, cd, False, fp8=True, ray_chunk=512)
-    s = make_static(ps, dev, F=128, early=4, late=0)
-    t = make_dynamic(pd, dev, F=128, early=4, late=0, T=8)
-    set_precision("bf16", s, t)
-    for m in (s, t):
-        m.update_freq_mask_alpha(75000, 150000)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen)
+    args = (ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd)
+    pix, a, b, dists, pso, pdo = oracle_render_grads(*args, emulate=dict(emulate_bf16=True, emulate_fp8_stage=S), ray_chunk=512)
+    go = prefixed_grads(pso, pdo)
+    s, t = bf16_pair(dev, ps, pd, 128, 4, 75000)
     with nca_option("STAGE_FP8", 1):
-        pr, ar, br, gr = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+        pr, ar, br, gr = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
         plan = _capi.last_plan()
     assert plan["fwd_resident"] == 1 and plan["bwd_resident"] == 1 and plan["bwd_kernel_mode"] == 5 and plan["stage_fp8"] == 1, plan
     with nca_option("STAGE_FP8", 1), nca_option("RESIDENT_MIN_TILES", -1):
-        p1, a1, b1, g1 = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+        p1, a1, b1, g1 = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
     assert torch.equal(pr, p1) and torch.equal(ar, a1) and torch.equal(br, b1)
     assert rel_err(ar.cpu(), a) < BF_OUT and rel_err(br.cpu(), b) < BF_OUT
     worst = worst_l2 = worst_scale = 0.0
@@ -278,9 +269,9 @@ def test_fp8_stage_at_natural_resident_threshold_vs_oracle(dev):
     # The same question for the other bf16 plan that ships: no forward store (stage_fp8 = 0, given per call) --
     # resident two-launch forward, recompute backward with bf16 operands everywhere -- against the oracle that rounds to bf16 only.
     from nerfca_amd import fused
-    go16 = _oracle_grads(ps, ss, pd, sd, win, win, o, d, ph, I0, z, cp, cs, cd, False, fp8=False, ray_chunk=512)[4]
+    go16 = prefixed_grads(*oracle_render_grads(*args, emulate=dict(emulate_bf16=True), ray_chunk=512)[4:])
     with fused.PlanScope(stage_fp8=0, bf16_store=0) as sc:
-        p0, a0, b0, g0 = _hip_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
+        p0, a0, b0, g0 = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd)
     assert sc.decided()["bwd_kernel_mode"] == 1 and sc.decided()["fwd_store_format"] == 0 and sc.decided()["fwd_resident"] == 1, sc.decided()
     assert torch.equal(p0, pr) and torch.equal(a0, ar) and torch.equal(b0, br)
     w16 = l16 = s16 = 0.0
@@ -309,36 +300,18 @@ def test_parity_mode_at_scale_vs_f64_oracle(dev):
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     S, R = 192, (8 * 8 * cus + 2) // 3 + 40
     gen = torch.Generator().manual_seed(5151)
-    ss, sd = O.NetSpec(num_filters=128), O.NetSpec(num_filters=128, num_time_dim=8)
-    ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
+    ss, sd, ps, pd = net_pair(128, 4, gen)
     win = O.freq_mask_alpha(12, 75000, 150000, 1)[0]
-    o, d, ph, z, I0, cp, cs, cd = _inputs(R, S, gen)
-
-    def oracle(dt):
-        pso = {k: v.clone().to(dt).requires_grad_(True) for k, v in ps.items()}
-        pdo = {k: v.clone().to(dt).requires_grad_(True) for k, v in pd.items()}
-        outs = []
-        for r0 in range(0, R, 512):
-            sl = slice(r0, min(R, r0 + 512))
-            n = sl.stop - sl.start
-            pts = O.query_points(o[sl], d[sl], z).to(dt)
-            raw_s = O.static_forward(pso, ss, pts, win.to(dt)).reshape(n, S, -1)
-            raw_d = O.dynamic_forward(pdo, sd, pts, ph[sl][:, None].repeat(1, S).flatten(), win.to(dt)).reshape(n, S, -1)
-            pix, a, b, dists = O.composite(raw_s, raw_d, I0[sl].to(dt), d[sl], z.to(dt))
-            ((pix * cp[sl]).sum() + (a * cs[sl].to(dt)).sum() * 50 + (b * cd[sl].to(dt)).sum() * 50).backward()
-            outs.append((pix.detach(), a.detach(), b.detach()))
-        g = {"s." + k: v.grad for k, v in pso.items()}
-        g.update({"t." + k: v.grad for k, v in pdo.items()})
-        return tuple(torch.cat([x[i] for x in outs]) for i in range(3)), dists, g
-
-    (pix, a, b), dists, g64 = oracle(torch.float64)
-    _, _, g32 = oracle(torch.float32)
+    o, d, ph, z, I0, cp, cs, cd = ray_inputs(R, S, gen)
+    args = (ps, ss, pd, sd, win, o, d, ph, I0, z, cp, cs, cd)
+    pix, a, b, dists, ps64, pd64 = oracle_render_grads(*args, dt=torch.float64, ray_chunk=512)
+    g64, g32 = prefixed_grads(ps64, pd64), prefixed_grads(*oracle_render_grads(*args, dt=torch.float32, ray_chunk=512)[4:])
     s = make_static(ps, dev, F=128, early=4, late=0)
     t = make_dynamic(pd, dev, F=128, early=4, late=0, T=8)
     set_precision("f32", s, t)
     for m in (s, t):
         m.update_freq_mask_alpha(75000, 150000)
-    ph_, ah, bh, gh = _hip_grads(s, t, dev, o, d, ph, I0, z, dists.to(torch.float64), cp, cs, cd)
+    ph_, ah, bh, gh = hip_render_grads(s, t, dev, o, d, ph, I0, z, dists.to(torch.float64), cp, cs, cd)
     assert _capi.last_plan()["bwd_kernel_mode"] == 3
     assert rel_err(ph_.cpu(), pix) < 1e-5 and rel_err(ah.cpu(), a) < 1e-5 and rel_err(bh.cpu(), b) < 1e-5
 

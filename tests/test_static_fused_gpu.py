@@ -2,30 +2,16 @@
 restatement, StaticTrainer.fused_gradients_on against the reference's own three-step trajectory (tests/golden/static_step.npz),
 the fused gradient against the autograd step's, the graph-replayed step against the host-launched one, two ray shards against one
 rank, and evaluate against the oracle."""
-import time
-
 import pytest
 import torch
 
 from conftest import rel_err
+from nca_testlib import dev, model_def  # noqa: F401
 from oracle import nerfca_oracle as O
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    t0 = time.time()
-    yield torch.device("cuda:0")
-    print(f"\n[test_static_fused_gpu] wall time {time.time() - t0:.1f} s")
-
-
-def _static_def(dev, F=64, early=4, L=12, pos_enc="free_windowed"):
-    return dict(num_early_layers=early, num_late_layers=0, num_filters=F, num_input_channels=3, num_output_channels=1, use_bias=True,
-                pos_enc=pos_enc, pos_enc_window_start=1, pos_enc_basis=L, fourier_sigma=2, fourier_gaussian=None, act_func="relu", device=dev)
 
 
 def _flat_of(model, flat):
@@ -85,7 +71,7 @@ def test_static_fused_steps_vs_reference(golden, dev):
     from nerfca_amd.model.CPPN import CPPN
     from nerfca_amd.train.trainer import StaticTrainer, TrainConfig
     g = golden("static_step")
-    s = CPPN(_static_def(dev))
+    s = CPPN(model_def(F=64, device=dev))
     s.load_state_dict(g.prefixed("init_sp_"))
     s = s.to(dev)
     R, S = g["o"].shape[0], g["z"].shape[0]

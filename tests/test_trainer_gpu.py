@@ -10,15 +10,9 @@ import pytest
 import torch
 
 from conftest import rel_err
-from test_hip_parity import make_dynamic, make_static
+from nca_testlib import dev, make_dynamic, make_static  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
 
 
 def _golden_data(g, dev):

@@ -10,18 +10,13 @@ import pytest
 import torch
 
 from conftest import ROOT, rel_err
+from nca_testlib import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5             # the project's f32 bound (tests/test_hip_parity.py)
 BF_OUT = 2e-3          # the project's bf16 output bound (tests/test_hip_parity.py)
 VIEWS = [(-5, 40), (60, -30), (0, 0), (137.5, -63)]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
 
 
 def geometries():

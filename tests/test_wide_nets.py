@@ -10,16 +10,12 @@ import pytest
 import torch
 
 from conftest import rel_err
+from nca_testlib import dev, grads_of, make_dynamic, make_static, model_def, spec_from  # noqa: F401
 from oracle import nerfca_oracle as O
 
 TOL = 1e-5
 STATIC_CASES = [(136, 1, 0), (136, 1, 2), (256, 1, 0)]
 CHANNEL_CASES = [(2, 3, "vanilla", 5), (4, 2, "fourier", 3), (1, 1, "none", 0)]
-
-
-def spec_from(F, early, late, pos_enc="free_windowed", L=12, T=0, cin=3, cout=1, coef=None):
-    return O.NetSpec(num_filters=F, num_early_layers=early, num_late_layers=late, num_input_channels=cin, num_output_channels=cout,
-                     pos_enc=pos_enc, pos_enc_basis=L, pos_enc_window_start=1, num_time_dim=T, fourier_coefficients=coef)
 
 
 # ------------------------------------------------------------------------------------------ the oracle on the reference's values (CPU)
@@ -98,39 +94,6 @@ int main() {
 
 
 # ------------------------------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need an MI355X"
-    return torch.device("cuda:0")
-
-
-def model_def(F, early, late, pos_enc="free_windowed", L=12, T=0, gauss=None, sigma=2, cin=3, cout=1, device="cpu"):
-    d = dict(num_early_layers=early, num_late_layers=late, num_filters=F, num_input_channels=cin, num_output_channels=cout,
-             use_bias=True, pos_enc=pos_enc, pos_enc_window_start=1, pos_enc_basis=L, fourier_sigma=sigma,
-             fourier_gaussian=gauss, act_func="relu", device=device)
-    if T:
-        d.update(num_input_times=1, use_time_latents=True, num_time_dim=T)
-    return d
-
-
-def make_static(params, dev, **kw):
-    from nerfca_amd.model.CPPN import CPPN
-    m = CPPN(model_def(device=dev, **kw))
-    m.load_state_dict(params)
-    return m.to(dev)
-
-
-def make_dynamic(params, dev, **kw):
-    from nerfca_amd.model.Temporal import Temporal
-    m = Temporal(model_def(device=dev, **kw))
-    m.load_state_dict(params)
-    return m.to(dev)
-
-
-def grads_of(model):
-    return {k: p.grad.detach().cpu() for k, p in model.named_parameters()}
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("F,early,late", STATIC_CASES)
 def test_points_wide_static_vs_reference(golden, dev, F, early, late):
