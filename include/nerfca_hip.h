@@ -576,6 +576,42 @@ int nca_image_normalize(int32_t n_img, int64_t n, const float* img, float* out, 
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_view_last_error(void);
 
+/* ---- drr: cone-beam projection of voxel volumes (drr.project_rays / project_sequence / volume_teacher) --------
+ * Line integrals of trilinearly interpolated voxel grids along the rays nca_view_rays writes, by the renderer's quadrature:
+ * pix = i0 - sum_s value(o + d z_s) dists_s.  Purely additive to ABI 13.  Like the view section, these entry points keep their OWN
+ * per-thread message (the accessor below); a refused call launches nothing and reads no pointer; a launch failure is reported once. */
+
+/* A regular grid of nodes, export.density_volume's linspace(lo, hi, n) on each axis. */
+typedef struct NcaGrid {          /* 64 bytes, no implicit padding */
+    double lo[3];                 /* position of node 0 on each axis */
+    double inv[3];                /* (n-1)/(hi-lo): nodes per unit length, computed by the host in f64 */
+    int32_t n[3];                 /* nodes per axis, each >= 2; vol is [n0][n1][n2], last axis fastest */
+    int32_t reserved;             /* 0 */
+} NcaGrid;
+
+/* vol f32 [n_vol][n0][n1][n2] contiguous, rays f64 [R,3] (nca_view_rays with out_f64 = 1), z f32 [S], dists f64 [S] -> pix f64 [n_vol][R].
+ * One sample, every operation a rounded f64 one in this order (no contraction): p_a = o_a + d_a (double)z_s; g_a = (p_a - lo_a) inv_a;
+ * i_a = floor(g_a); f_a = g_a - i_a; the eight neighbours (i_a, i_a + 1), one with any index outside [0, n_a - 1] reading as 0, are
+ * interpolated as (1 - f) v0 + f v1 along the last axis first, then the middle one, then the first; term = value dists_s.  This is
+ * grid_sample(mode="bilinear", padding_mode="zeros", align_corners=True) with the coordinate triple reversed.  A sample with a g_a outside
+ * (-1, n_a) contributes exactly 0 and loads nothing.  All n_vol volumes are marched in one pass: a sample's indices and weights are computed
+ * once per group of up to 8 volumes; each volume's sum is formed in the same order whatever the grouping, so the result does not depend
+ * on n_vol, on how a ray set is split into calls, or on the run.  No atomics.  `grid` is a host pointer.
+ * NCA_E_INVALID (the message names the value): a NULL pointer; n_vol, R or S <= 0; an n_a < 2; reserved != 0; a non-finite lo or inv;
+ * inv_a <= 0; a voxel count that overflows int64. */
+int nca_drr_project(const NcaGrid* grid, const float* vol, int32_t n_vol, int64_t R, int32_t S, const double* origins, const double* dirs,
+                    const float* z, const double* dists, double i0, double* pix, void* stream);
+
+/* Threads that share one ray (process-wide): 1 = one thread marches all S samples in order; 4 = part j of four takes the samples
+ * s = j, j + 4, ... (the four parts of a ray in four waves of one block) and the four sub-sums are folded in part order.  Both are
+ * deterministic; they differ from each other in the last bits (the order of the sum).  The default is the faster of the two as measured by
+ * tools/drr_bench.py; the other stays for that tool.  set: NCA_E_INVALID for any other value. */
+int nca_drr_set_split(int32_t split);
+int nca_drr_get_split(void);
+
+/* The message of the calling thread's last failed call of this section. */
+const char* nca_drr_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

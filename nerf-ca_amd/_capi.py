@@ -127,6 +127,11 @@ class NcaView(C.Structure):
     _fields_ = [("pose", C.c_float * 12), ("W", C.c_int32), ("H", C.c_int32), ("d_det", C.c_float * 2), ("off_det", C.c_float * 2), ("dsd", C.c_float)]
 
 
+class NcaGrid(C.Structure):
+    """A regular grid of nodes for nca_drr_project: linspace(lo, hi, n) per axis, inv = (n - 1) / (hi - lo) (include/nerfca_hip.h)."""
+    _fields_ = [("lo", C.c_double * 3), ("inv", C.c_double * 3), ("n", C.c_int32 * 3), ("reserved", C.c_int32)]
+
+
 class NcaError(RuntimeError):
     pass
 
@@ -191,6 +196,10 @@ SYMBOLS = {
     "nca_image_normalize_workspace": (_I64, [_I64]),
     "nca_image_normalize": (C.c_int, [_I32, _I64, _P, _P, _P, _P, _I64, _P]),
     "nca_view_last_error": (C.c_char_p, []),
+    "nca_drr_project": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, _I64, _I32, _P, _P, _P, _P, C.c_double, _P, _P]),
+    "nca_drr_set_split": (C.c_int, [_I32]),
+    "nca_drr_get_split": (C.c_int, []),
+    "nca_drr_last_error": (C.c_char_p, []),
 }
 
 
@@ -223,6 +232,13 @@ def check_view(rc: int) -> int:
     """``check`` for the view-rendering entry points (nca_view_*, nca_image_normalize*): they keep their own message."""
     if rc < 0:
         raise NcaError(f"libnerfca_hip: {lib().nca_view_last_error().decode()} (code {rc})")
+    return rc
+
+
+def check_drr(rc: int) -> int:
+    """``check`` for the volume-projection entry points (nca_drr_*): they keep their own message."""
+    if rc < 0:
+        raise NcaError(f"libnerfca_hip: {lib().nca_drr_last_error().decode()} (code {rc})")
     return rc
 
 

@@ -1,0 +1,189 @@
+// nca_drr.hip -- cone-beam projection of voxel volumes (include/nerfca_hip.h, "drr"): line integrals of trilinearly interpolated f32
+// grids along f64 rays, pix = i0 - sum_s value(o + d z_s) dists_s, the quadrature of the renderer.  What turns a CT / phantom volume
+// into training projections (drr.volume_teacher) and an exported 4-D density grid back into images (drr.project_sequence).  Forward
+// only.  This translation unit keeps its own thread-local error message (nca_drr_last_error): it shares no state with nca_api.hip or
+// nca_view.hip.
+#include <hip/hip_runtime.h>
+#include <atomic>
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdint.h>
+#include "../../../include/nerfca_hip.h"
+
+static_assert(sizeof(NcaGrid) == 64, "NcaGrid is 64 bytes without padding");
+
+static thread_local char g_drr_err[256] = "";
+
+static int dfail(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_drr_err, sizeof(g_drr_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+extern "C" const char* nca_drr_last_error(void) { return g_drr_err; }
+
+constexpr int DRR_BLOCK = 256;
+constexpr int DRR_MAX_GROUP = 8;          // volumes one launch keeps accumulators for
+constexpr int DRR_DEFAULT_SPLIT = 4;      // the structure tools/drr_bench.py measured as the faster one in every row
+
+static std::atomic<int> g_drr_split{DRR_DEFAULT_SPLIT};
+
+extern "C" int nca_drr_set_split(int32_t split) {
+    if (split != 1 && split != 4) return dfail(NCA_E_INVALID, "nca_drr_set_split: split = %d is neither 1 nor 4", (int)split);
+    g_drr_split.store(split);
+    return NCA_OK;
+}
+
+extern "C" int nca_drr_get_split(void) { return g_drr_split.load(); }
+
+// (1 - f) v0 + f v1: two rounded products and one rounded sum
+__device__ __forceinline__ double lerp_rn(double omf, double f, double v0, double v1) { return __dadd_rn(__dmul_rn(omf, v0), __dmul_rn(f, v1)); }
+
+// One thread per (ray, part): part j of the K that share a ray marches the samples s = j, j + K, ... in order with one f64 accumulator per
+// volume in registers; the K sub-sums are then folded in part order through LDS.  K = 1 is the plain loop over s.  The K parts of a ray sit in
+// K different waves of the block (K = 4: wave j of the four is part j of 64 adjacent rays), so in both forms the 64 split of a wave are 64
+// adjacent detector pixels (p = w*H + h) at ONE depth step and their gathers fall in a compact block of voxels; K = 4 puts four times the
+// waves on the device.  The order of a volume's sum is a function of (S, K) alone: no atomics, nothing depends on the block, the chunk or
+// the other volumes of the group.
+//
+// A sample's indices and weights are computed once and applied to all NV volumes.  A sample with every neighbour inside the grid takes the
+// unguarded path (its two last-axis neighbours are adjacent dwords, which the compiler may fetch as one 8-byte load: that needs no
+// alignment beyond the dword's on this target); one in the one-cell rim guards each of its eight loads; one outside loads nothing.
+template <int NV, int K>
+__global__ void __launch_bounds__(DRR_BLOCK) drr_kernel(NcaGrid g, const float* __restrict__ vol, int64_t voxels, int64_t R, int32_t S,
+                                                        const double* __restrict__ origins, const double* __restrict__ dirs, const float* __restrict__ z,
+                                                        const double* __restrict__ dists, double i0, double* __restrict__ pix) {
+    constexpr int RAYS = DRR_BLOCK / K;          // rays of one block
+    const int slot = threadIdx.x % RAYS, part = threadIdx.x / RAYS;          // part: which of the K sub-sums of its ray this thread forms
+    const int64_t ray = (int64_t)blockIdx.x * RAYS + slot;
+    const bool live = ray < R;
+    double acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
+    if (live) {
+        const double o0 = origins[3 * ray], o1 = origins[3 * ray + 1], o2 = origins[3 * ray + 2];
+        const double d0 = dirs[3 * ray], d1 = dirs[3 * ray + 1], d2 = dirs[3 * ray + 2];
+        const int32_t n0 = g.n[0], n1 = g.n[1], n2 = g.n[2];
+        const int64_t row = n2, slab = (int64_t)n1 * n2;
+        for (int32_t s = part; s < S; s += K) {
+            const double zz = (double)z[s];
+            const double g0 = __dmul_rn(__dsub_rn(__dadd_rn(o0, __dmul_rn(d0, zz)), g.lo[0]), g.inv[0]);
+            const double g1 = __dmul_rn(__dsub_rn(__dadd_rn(o1, __dmul_rn(d1, zz)), g.lo[1]), g.inv[1]);
+            const double g2 = __dmul_rn(__dsub_rn(__dadd_rn(o2, __dmul_rn(d2, zz)), g.lo[2]), g.inv[2]);
+            // outside (-1, n) on any axis (or NaN): every neighbour is outside or has weight 0, the term is exactly 0 -- load nothing
+            if (!(g0 > -1.0 && g0 < (double)n0 && g1 > -1.0 && g1 < (double)n1 && g2 > -1.0 && g2 < (double)n2)) continue;
+            const double fl0 = floor(g0), fl1 = floor(g1), fl2 = floor(g2);
+            const double f0 = __dsub_rn(g0, fl0), f1 = __dsub_rn(g1, fl1), f2 = __dsub_rn(g2, fl2);
+            const double m0 = __dsub_rn(1.0, f0), m1 = __dsub_rn(1.0, f1), m2 = __dsub_rn(1.0, f2);
+            const int32_t i0a = (int32_t)fl0, i1a = (int32_t)fl1, i2a = (int32_t)fl2;          // each in [-1, n - 1]
+            const double w = dists[s];
+            const int64_t base = ((int64_t)i0a * n1 + i1a) * n2 + i2a;                          // of neighbour (0,0,0); used only where that is valid
+            if (i0a >= 0 && i0a < n0 - 1 && i1a >= 0 && i1a < n1 - 1 && i2a >= 0 && i2a < n2 - 1) {
+#pragma unroll
+                for (int v = 0; v < NV; ++v) {
+                    const float* p = vol + (int64_t)v * voxels + base;
+                    const double c00 = lerp_rn(m2, f2, (double)p[0], (double)p[1]);
+                    const double c01 = lerp_rn(m2, f2, (double)p[row], (double)p[row + 1]);
+                    const double c10 = lerp_rn(m2, f2, (double)p[slab], (double)p[slab + 1]);
+                    const double c11 = lerp_rn(m2, f2, (double)p[slab + row], (double)p[slab + row + 1]);
+                    const double val = lerp_rn(m0, f0, lerp_rn(m1, f1, c00, c01), lerp_rn(m1, f1, c10, c11));
+                    acc[v] = __dadd_rn(acc[v], __dmul_rn(val, w));
+                }
+            } else {
+                const bool a0 = i0a >= 0, b0 = i0a + 1 < n0, a1 = i1a >= 0, b1 = i1a + 1 < n1, a2 = i2a >= 0, b2 = i2a + 1 < n2;
+#pragma unroll
+                for (int v = 0; v < NV; ++v) {
+                    const float* p = vol + (int64_t)v * voxels;
+                    auto at = [&](bool ok, int64_t off) -> double { return ok ? (double)p[base + off] : 0.0; };
+                    const double c00 = lerp_rn(m2, f2, at(a0 && a1 && a2, 0), at(a0 && a1 && b2, 1));
+                    const double c01 = lerp_rn(m2, f2, at(a0 && b1 && a2, row), at(a0 && b1 && b2, row + 1));
+                    const double c10 = lerp_rn(m2, f2, at(b0 && a1 && a2, slab), at(b0 && a1 && b2, slab + 1));
+                    const double c11 = lerp_rn(m2, f2, at(b0 && b1 && a2, slab + row), at(b0 && b1 && b2, slab + row + 1));
+                    const double val = lerp_rn(m0, f0, lerp_rn(m1, f1, c00, c01), lerp_rn(m1, f1, c10, c11));
+                    acc[v] = __dadd_rn(acc[v], __dmul_rn(val, w));
+                }
+            }
+        }
+    }
+    // every thread of the block gets here (nothing returned early): the barrier is safe
+    if constexpr (K > 1) {
+        __shared__ double s_part[K - 1][NV][RAYS];
+        if (part > 0) {
+#pragma unroll
+            for (int v = 0; v < NV; ++v) s_part[part - 1][v][slot] = acc[v];
+        }
+        __syncthreads();
+        if (part == 0) {
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+#pragma unroll
+                for (int q = 1; q < K; ++q) acc[v] = __dadd_rn(acc[v], s_part[q - 1][v][slot]);          // ((a0 + a1) + a2) + a3
+            }
+        }
+    }
+    if (live && part == 0) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) pix[(int64_t)v * R + ray] = __dsub_rn(i0, acc[v]);
+    }
+}
+
+template <int NV>
+static void launch_group(int split, dim3 grid, hipStream_t st, const NcaGrid& g, const float* vol, int64_t voxels, int64_t R, int32_t S, const double* origins,
+                         const double* dirs, const float* z, const double* dists, double i0, double* pix) {
+    if (split == 4)
+        hipLaunchKernelGGL((drr_kernel<NV, 4>), grid, dim3(DRR_BLOCK), 0, st, g, vol, voxels, R, S, origins, dirs, z, dists, i0, pix);
+    else
+        hipLaunchKernelGGL((drr_kernel<NV, 1>), grid, dim3(DRR_BLOCK), 0, st, g, vol, voxels, R, S, origins, dirs, z, dists, i0, pix);
+}
+
+extern "C" int nca_drr_project(const NcaGrid* grid, const float* vol, int32_t n_vol, int64_t R, int32_t S, const double* origins, const double* dirs,
+                               const float* z, const double* dists, double i0, double* pix, void* stream) {
+    if (!grid) return dfail(NCA_E_INVALID, "nca_drr_project: the grid descriptor is NULL");
+    if (!vol) return dfail(NCA_E_INVALID, "nca_drr_project: vol is NULL");
+    if (!origins) return dfail(NCA_E_INVALID, "nca_drr_project: origins is NULL");
+    if (!dirs) return dfail(NCA_E_INVALID, "nca_drr_project: dirs is NULL");
+    if (!z) return dfail(NCA_E_INVALID, "nca_drr_project: z is NULL");
+    if (!dists) return dfail(NCA_E_INVALID, "nca_drr_project: dists is NULL");
+    if (!pix) return dfail(NCA_E_INVALID, "nca_drr_project: pix is NULL");
+    if (n_vol <= 0) return dfail(NCA_E_INVALID, "nca_drr_project: n_vol = %d is not positive", (int)n_vol);
+    if (R <= 0) return dfail(NCA_E_INVALID, "nca_drr_project: R = %lld is not positive", (long long)R);
+    if (S <= 0) return dfail(NCA_E_INVALID, "nca_drr_project: S = %d is not positive", (int)S);
+    const NcaGrid g = *grid;
+    if (g.reserved != 0) return dfail(NCA_E_INVALID, "nca_drr_project: reserved = %d is not 0", (int)g.reserved);
+    for (int a = 0; a < 3; ++a) {
+        if (g.n[a] < 2) return dfail(NCA_E_INVALID, "nca_drr_project: n[%d] = %d is less than 2 nodes", a, (int)g.n[a]);
+        if (!isfinite(g.lo[a])) return dfail(NCA_E_INVALID, "nca_drr_project: lo[%d] = %g is not finite", a, g.lo[a]);
+        if (!isfinite(g.inv[a])) return dfail(NCA_E_INVALID, "nca_drr_project: inv[%d] = %g is not finite", a, g.inv[a]);
+        if (!(g.inv[a] > 0.0)) return dfail(NCA_E_INVALID, "nca_drr_project: inv[%d] = %g is not positive", a, g.inv[a]);
+    }
+    // n0 n1 < 2^62 always; the bytes of all volumes must fit int64
+    const int64_t n01 = (int64_t)g.n[0] * g.n[1];
+    if (n01 > (INT64_MAX / 4 / n_vol) / g.n[2])
+        return dfail(NCA_E_INVALID, "nca_drr_project: %d volumes of %d x %d x %d voxels overflow int64", (int)n_vol, (int)g.n[0], (int)g.n[1], (int)g.n[2]);
+    const int64_t voxels = n01 * g.n[2];
+    if (R > INT64_MAX / 8 / n_vol) return dfail(NCA_E_INVALID, "nca_drr_project: R = %lld rays x %d volumes overflows int64", (long long)R, (int)n_vol);
+    const int split = g_drr_split.load();
+    const int64_t rays_per_block = DRR_BLOCK / split, blocks = (R + rays_per_block - 1) / rays_per_block;
+    if (blocks > 0x7fffffffLL) return dfail(NCA_E_INVALID, "nca_drr_project: R = %lld is more than one launch covers", (long long)R);
+    const dim3 grd((unsigned)blocks);
+    const hipStream_t st = (hipStream_t)stream;
+    for (int32_t v0 = 0; v0 < n_vol;) {          // groups of 8, 4, 2, 1 volumes: each volume's sum is the same whatever group it is in
+        const int32_t left = n_vol - v0;
+        const int32_t nv = left >= DRR_MAX_GROUP ? DRR_MAX_GROUP : (left >= 4 ? 4 : (left >= 2 ? 2 : 1));
+        const float* vp = vol + (int64_t)v0 * voxels;
+        double* pp = pix + (int64_t)v0 * R;
+        switch (nv) {
+            case 8: launch_group<8>(split, grd, st, g, vp, voxels, R, S, origins, dirs, z, dists, i0, pp); break;
+            case 4: launch_group<4>(split, grd, st, g, vp, voxels, R, S, origins, dirs, z, dists, i0, pp); break;
+            case 2: launch_group<2>(split, grd, st, g, vp, voxels, R, S, origins, dirs, z, dists, i0, pp); break;
+            default: launch_group<1>(split, grd, st, g, vp, voxels, R, S, origins, dirs, z, dists, i0, pp); break;
+        }
+        v0 += nv;
+    }
+    const hipError_t e = hipGetLastError();          // once, after the last group
+    if (e != hipSuccess) return dfail(NCA_E_HIP, "nca_drr_project: %s", hipGetErrorString(e));
+    return NCA_OK;
+}

@@ -1,0 +1,193 @@
+"""Cone-beam projection of voxel volumes on the device (csrc/view/nca_drr.hip): digitally reconstructed radiographs.
+
+The reference makes its training projections from a CT or phantom volume with TIGRE (preprocess/datatoray.py,
+tigre_helpers.py: ``tigre.Ax``), a CUDA library; here the same step is ``nca_drr_project``: line integrals of a trilinearly
+interpolated f32 grid along the rays ``nca_view_rays`` generates, by the renderer's own quadrature
+``pix = I0 - sum_s sigma(o + d z_s) dists_s``.  Two uses:
+
+* coming in: ``volume_teacher`` is a ``render=`` hook of ``synthetic.make_dataset``, so a dataset can be made from a volume pair
+  instead of a teacher network pair;
+* going out: ``project_sequence`` / ``project_view`` reproject the grids ``export.density_volumes`` writes through the C-arm geometry,
+  with the keys and shapes of ``export.render_sequence`` / ``render_view``.
+
+A grid is ``export.density_volume``'s: ``linspace(lo, hi, n)`` nodes per axis, the volume ``[n0, n1, n2]`` with the last axis fastest;
+outside the grid the volume is 0.  There is no torch implementation behind these functions.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Callable, Optional, Sequence, Tuple
+
+import torch
+
+from . import _capi
+from . import export as _export
+from . import fused as _fused
+
+Bounds = Tuple[Tuple[float, float], ...]
+UNIT_BOUNDS: Bounds = ((-1.0, 1.0),) * 3
+
+
+def grid_desc(shape: Sequence[int], bounds: Bounds) -> "_capi.NcaGrid":
+    """The NcaGrid of a volume of ``shape`` ``(n0, n1, n2)`` whose nodes are ``linspace(lo, hi, n)`` on each axis of ``bounds``:
+    ``lo`` and ``inv = (n - 1) / (hi - lo)``, in f64."""
+    shape = tuple(int(n) for n in shape)
+    if len(shape) != 3 or len(bounds) != 3 or any(len(b) != 2 for b in bounds):
+        raise _capi.NcaError(f"a grid has three axes with (lo, hi) each: got shape {shape} and bounds {bounds!r}")
+    lo = [float(b[0]) for b in bounds]
+    hi = [float(b[1]) for b in bounds]
+    for a in range(3):
+        if shape[a] < 2:
+            raise _capi.NcaError(f"a grid has at least 2 nodes per axis: axis {a} has {shape[a]}")
+        if not (math.isfinite(lo[a]) and math.isfinite(hi[a]) and hi[a] > lo[a]):
+            raise _capi.NcaError(f"bounds of axis {a}: ({lo[a]}, {hi[a]}) is not a finite interval lo < hi")
+    inv = [(shape[a] - 1) / (hi[a] - lo[a]) for a in range(3)]
+    return _capi.NcaGrid(lo=(C.c_double * 3)(*lo), inv=(C.c_double * 3)(*inv), n=(C.c_int32 * 3)(*shape), reserved=0)
+
+
+def _default_dists(z: torch.Tensor) -> torch.Tensor:
+    from .train.model_helpers import _interval_lengths
+    return _interval_lengths(z, torch.empty(0, dtype=torch.float64, device=z.device))
+
+
+@torch.no_grad()
+def project_rays(volumes: torch.Tensor, origins: torch.Tensor, dirs: torch.Tensor, z: torch.Tensor, dists: Optional[torch.Tensor] = None, *,
+                 i0: float, bounds: Bounds) -> torch.Tensor:
+    """``i0 - sum_s volume(o + d z_s) dists_s`` of f32 ``volumes`` ``[n0,n1,n2]`` (returns f64 ``[R]``) or ``[n_vol,n0,n1,n2]``
+    (returns f64 ``[n_vol,R]``; the volumes share one grid and are marched in one pass) along the rays ``origins`` / ``dirs``
+    ``[R,3]`` (f64, or f32 widened) at the depths ``z`` ``[S]`` shared by all rays.  ``dists`` ``[S]`` defaults to
+    ``model_helpers._interval_lengths(z)``.  ``bounds`` places the grid (``grid_desc``)."""
+    for t, what in ((volumes, "volumes"), (origins, "ray origins"), (dirs, "ray directions"), (z, "depth values")):
+        _fused._require_cuda(t, what)
+    dev = volumes.device
+    if dists is not None:
+        _fused._require_cuda(dists, "interval lengths")
+    if any(t.device != dev for t in (origins, dirs, z) + (() if dists is None else (dists,))):
+        raise _capi.NcaError("project_rays: volumes, rays, depths and interval lengths must live on one device")
+    if volumes.dtype != torch.float32 or volumes.dim() not in (3, 4) or not volumes.is_contiguous() or volumes.numel() == 0:
+        raise _capi.NcaError(f"project_rays takes contiguous float32 volumes [n0,n1,n2] or [n_vol,n0,n1,n2], got {volumes.dtype} "
+                             f"{tuple(volumes.shape)}{'' if volumes.is_contiguous() else ' (not contiguous)'}")
+    if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape != dirs.shape or origins.shape[0] == 0:
+        raise _capi.NcaError(f"project_rays takes ray origins and directions [R,3], got {tuple(origins.shape)} and {tuple(dirs.shape)}")
+    if any(t.dtype not in (torch.float32, torch.float64) for t in (origins, dirs)):
+        raise _capi.NcaError("rays are float32 or float64")
+    if z.dim() != 1 or z.shape[0] == 0:
+        raise _capi.NcaError("project_rays takes ONE depth vector [S] shared by all rays")
+    z = z.detach().to(torch.float32).contiguous()
+    dists = _default_dists(z) if dists is None else dists.detach()
+    if dists.shape != z.shape:
+        raise _capi.NcaError(f"interval lengths {tuple(dists.shape)} do not match the depth vector {tuple(z.shape)}")
+    dists = dists.to(torch.float64).contiguous()
+    o = origins.detach().to(torch.float64).contiguous()
+    d = dirs.detach().to(torch.float64).contiguous()
+    desc = grid_desc(volumes.shape[-3:], bounds)
+    n_vol = 1 if volumes.dim() == 3 else volumes.shape[0]
+    R, S = o.shape[0], z.shape[0]
+    pix = torch.empty((n_vol, R), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _capi.check_drr(_capi.lib().nca_drr_project(C.byref(desc), _capi.ptr(volumes), n_vol, R, S, _capi.ptr(o), _capi.ptr(d), _capi.ptr(z),
+                                                    _capi.ptr(dists), float(i0), _capi.ptr(pix), _fused._stream()))
+    return pix[0] if volumes.dim() == 3 else pix
+
+
+@torch.no_grad()
+def project_sequence(sigma_static: torch.Tensor, sigma_dynamic: Optional[torch.Tensor], geo: dict, views: Sequence[Sequence[float]], samples: int, *,
+                     bounds: Bounds = UNIT_BOUNDS, z: Optional[torch.Tensor] = None, chunk_rays: int = 65536, normalize: bool = False) -> dict:
+    """Project the static volume ``[n0,n1,n2]`` and the P dynamic volumes ``[P,n0,n1,n2]`` (what ``export.density_volumes`` returns:
+    sigma already scaled) through every view ``(theta, phi[, larm])`` of ``views``: f32 images ``pred`` and ``pred_dynamic``
+    ``[V,P,W,H]`` and ``pred_static`` ``[V,W,H]``, the keys, shapes and composition of ``export.render_sequence``.  Per view and ray
+    chunk there is one projection of the static volume and one of all P dynamic volumes.  ``sigma_dynamic=None`` behaves like
+    ``temp_model=None`` there (P = 1, ``pred = pred_static``, ``pred_dynamic`` is ``I0`` everywhere).  ``z`` defaults to the un-jittered
+    ``create_depth_values(near, far, samples)``; ``I0 = geo["max_pixel_value"]``; ``normalize=True`` adds the ``*_norm`` images and
+    ``minmax`` as there."""
+    from .train.data_helpers import create_depth_values
+    _fused._require_cuda(sigma_static, "the static volume")
+    dev = sigma_static.device
+    if sigma_static.dim() != 3:
+        raise _capi.NcaError(f"the static volume is [n0,n1,n2], got {tuple(sigma_static.shape)}")
+    if sigma_dynamic is not None:
+        _fused._require_cuda(sigma_dynamic, "the dynamic volumes")
+        if sigma_dynamic.dim() != 4 or sigma_dynamic.shape[1:] != sigma_static.shape or sigma_dynamic.shape[0] == 0 or sigma_dynamic.device != dev:
+            raise _capi.NcaError(f"the dynamic volumes are [P,n0,n1,n2] on the static volume's grid and device, got {tuple(sigma_dynamic.shape)} "
+                                 f"for a static volume {tuple(sigma_static.shape)}")
+    views = [tuple(float(a) for a in v) for v in views]
+    if not views or any(len(v) not in (2, 3) for v in views):
+        raise ValueError("views is a non-empty list of (theta, phi) or (theta, phi, larm)")
+    W, H = (int(v) for v in geo["nDetector"])
+    npix, V, P = W * H, len(views), (1 if sigma_dynamic is None else sigma_dynamic.shape[0])
+    if z is None:
+        z = create_depth_values(geo["near_thresh"], geo["far_thresh"], int(samples), dev)
+    z = z.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if z.dim() != 1:
+        raise _capi.NcaError("volume projection takes ONE depth vector [S] shared by all rays")
+    dists = _default_dists(z).to(torch.float64).contiguous()
+    i0 = float(torch.tensor(geo["max_pixel_value"], dtype=torch.float32))          # the f32 value render_sequence starts every ray sum from
+    pred = torch.empty((V, P, npix), dtype=torch.float32, device=dev)
+    pred_d = torch.empty((V, P, npix), dtype=torch.float32, device=dev)
+    pred_s = torch.empty((V, npix), dtype=torch.float32, device=dev)
+    plan = _export.chunk_plan(npix, int(chunk_rays))
+    with torch.cuda.device(dev):
+        for v, view in enumerate(views):
+            desc = _export.pack_view(geo, *view)
+            for p0, n in plan:
+                o, d = _export._rays_of(desc, p0, n, dev, torch.float64)
+                pix_s = project_rays(sigma_static, o, d, z, dists, i0=i0, bounds=bounds)
+                if sigma_dynamic is None:
+                    _export.compose_images(pix_s, None, i0, pred[v, 0, p0:p0 + n], pred_s[v, p0:p0 + n], pred_d[v, 0, p0:p0 + n])
+                    continue
+                pix_d = project_rays(sigma_dynamic, o, d, z, dists, i0=i0, bounds=bounds)
+                for j in range(P):
+                    _export.compose_images(pix_s, pix_d[j], i0, pred[v, j, p0:p0 + n], pred_s[v, p0:p0 + n], pred_d[v, j, p0:p0 + n])
+    out = {"pred": pred.reshape(V, P, W, H), "pred_static": pred_s.reshape(V, W, H), "pred_dynamic": pred_d.reshape(V, P, W, H)}
+    if normalize:
+        out["minmax"] = {}
+        for k in ("pred", "pred_static", "pred_dynamic"):
+            img = out[k]
+            norm, mm = _export.normalize_images(img.reshape(-1, W, H))
+            out[k + "_norm"], out["minmax"][k] = norm.reshape(img.shape), mm.reshape(img.shape[:-2] + (2,))
+    return out
+
+
+def project_view(sigma_static: torch.Tensor, sigma_dynamic: Optional[torch.Tensor], geo: dict, theta: float, phi: float, samples: int, *,
+                 larm: float = 0, bounds: Bounds = UNIT_BOUNDS, z: Optional[torch.Tensor] = None, chunk_rays: int = 65536, normalize: bool = False) -> dict:
+    """One view of one volume pair: ``project_sequence`` for ``[(theta, phi, larm)]`` and a static volume ``[n0,n1,n2]`` with a
+    dynamic volume ``[n0,n1,n2]`` (or ``None``), the leading axes dropped -- ``pred``, ``pred_static``, ``pred_dynamic`` as f32
+    ``[W,H]`` like ``export.render_view``."""
+    if sigma_dynamic is not None and sigma_dynamic.dim() != 3:
+        raise _capi.NcaError(f"project_view takes ONE dynamic volume [n0,n1,n2], got {tuple(sigma_dynamic.shape)}")
+    out = project_sequence(sigma_static, None if sigma_dynamic is None else sigma_dynamic[None], geo, [(theta, phi, larm)], samples, bounds=bounds, z=z,
+                           chunk_rays=chunk_rays, normalize=normalize)
+    res = {k: t.reshape(t.shape[-2:]) for k, t in out.items() if k != "minmax"}
+    if normalize:
+        res["minmax"] = {k: t.reshape(2) for k, t in out["minmax"].items()}
+    return res
+
+
+def volume_teacher(bounds: Bounds) -> Callable:
+    """A ``render=`` hook of ``synthetic.make_dataset`` for ``teacher=(vol_static [n0,n1,n2], vol_dynamic [P,n0,n1,n2])``: the target
+    images are projections of the volume pair instead of renders of a network pair.  ``pix = (pix_s + pix_d[phase]) - I0`` in f64 in
+    that order, as ``nca_view_compose`` forms the composite.  The dynamic stack is one heart cycle: phase ``p`` reads volume ``p mod P``.
+    All rays of one call share one phase and one I0 (how ``make_dataset`` calls its hook); anything else is refused."""
+
+    def render(vol_static, vol_dynamic, origins, dirs, phase_ids, I0, z, dists):
+        _fused._require_cuda(phase_ids, "phase ids")
+        _fused._require_cuda(I0, "I0")
+        if vol_dynamic.dim() != 4 or vol_dynamic.shape[1:] != vol_static.shape:
+            raise _capi.NcaError(f"volume_teacher takes teacher=(static [n0,n1,n2], dynamic [P,n0,n1,n2]), got {tuple(vol_static.shape)} and "
+                                 f"{tuple(vol_dynamic.shape)}")
+        if phase_ids.numel() != origins.shape[0] or I0.numel() != origins.shape[0]:
+            raise _capi.NcaError("volume_teacher: one phase id and one I0 per ray")
+        lo, hi, i_lo, i_hi = (float(x) for x in torch.stack([phase_ids.min().double(), phase_ids.max().double(), I0.min().double(), I0.max().double()]).tolist())
+        if lo != hi:
+            raise _capi.NcaError(f"volume_teacher projects ONE phase per call: the rays carry phases {int(lo)} .. {int(hi)}")
+        if i_lo != i_hi:
+            raise _capi.NcaError(f"volume_teacher takes ONE I0 per call: the rays carry {i_lo} .. {i_hi}")
+        if lo < 0:
+            raise _capi.NcaError(f"volume_teacher: phase {int(lo)} is negative")
+        phase = int(lo) % vol_dynamic.shape[0]          # the heart cycle is periodic: make_dataset's held-out image is phase 3 whatever n_phases
+        pix_s = project_rays(vol_static, origins, dirs, z, dists, i0=i_lo, bounds=bounds)
+        pix_d = project_rays(vol_dynamic[phase], origins, dirs, z, dists, i0=i_lo, bounds=bounds)
+        return (pix_s + pix_d) - i_lo
+
+    return render
