@@ -576,7 +576,7 @@ int nca_image_normalize(int32_t n_img, int64_t n, const float* img, float* out, 
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_view_last_error(void);
 
-/* ---- drr: cone-beam projection of voxel volumes (drr.project_rays / project_sequence / volume_teacher) --------
+/* ---- drr: cone-beam projection of voxel volumes and its adjoint (drr.project_rays / project_sequence / volume_teacher / fit_volumes) --------
  * Line integrals of trilinearly interpolated voxel grids along the rays nca_view_rays writes, by the renderer's quadrature:
  * pix = i0 - sum_s value(o + d z_s) dists_s.  Purely additive to ABI 13.  Like the view section, these entry points keep their OWN
  * per-thread message (the accessor below); a refused call launches nothing and reads no pointer; a launch failure is reported once. */
@@ -608,6 +608,28 @@ int nca_drr_project(const NcaGrid* grid, const float* vol, int32_t n_vol, int64_
  * tools/drr_bench.py; the other stays for that tool.  set: NCA_E_INVALID for any other value. */
 int nca_drr_set_split(int32_t split);
 int nca_drr_get_split(void);
+
+/* The adjoint of nca_drr_project in the volumes: g_pix f64 [n_vol][R] (the gradient of a scalar in pix) -> ADDED INTO g_vol f64
+ * [n_vol][n0*n1*n2] (the caller zeroes it); rays, z, dists and `grid` as above.  For sample (ray, s), g_a, i_a, f_a and m_a = 1 - f_a are
+ * exactly those of nca_drr_project: the same rounded f64 operations, the same skip test g_a in (-1, n_a), never a clamp.  For each of the
+ * eight neighbours (a, b, c) in {0,1}^3 whose node (i_0 + a, i_1 + b, i_2 + c) is inside the grid and for each volume v:
+ *     w_abc = (x0 x1) x2, where x_k is f_k when the offset on axis k is 1 and m_k when it is 0;
+ *     contrib = (-(g_pix[v][ray] dists_s)) w_abc;          g_vol[v][node] += contrib,
+ * every product a rounded f64 product in that order.  Neighbours outside the grid contribute nothing and are never addressed; i0 does not
+ * enter.  Only the order of a node's sum is undefined: the adds are f64 atomics (one hardware add each, no compare-and-swap loop), so the
+ * last bits can differ from run to run.  A sample's indices and weights are computed once per group of up to 8 volumes.  No
+ * synchronisation beyond the stream's order: a later kernel on `stream` reads the finished sums.
+ * NCA_E_INVALID (the message names the value): the refusals of nca_drr_project, with g_pix and g_vol for vol and pix; an S within 4 of
+ * INT32_MAX. */
+int nca_drr_backproject(const NcaGrid* grid, int32_t n_vol, int64_t R, int32_t S, const double* origins, const double* dirs, const float* z,
+                        const double* dists, const double* g_pix, double* g_vol, void* stream);
+
+/* How nca_drr_backproject adds (process-wide): 0 = one atomic per (sample, neighbour, volume); 1 = a thread sums the contributions of
+ * consecutive samples of its ray that stay in one cell in registers and adds them when the cell changes.  They differ in the order of a
+ * node's sum only.  The default is the faster of the two as measured by tools/drr_grad_bench.py; the other stays for that tool.
+ * set: NCA_E_INVALID for any other value. */
+int nca_drr_set_backproject_runs(int32_t runs);
+int nca_drr_get_backproject_runs(void);
 
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_drr_last_error(void);

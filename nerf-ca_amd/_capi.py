@@ -199,6 +199,9 @@ SYMBOLS = {
     "nca_drr_project": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, _I64, _I32, _P, _P, _P, _P, C.c_double, _P, _P]),
     "nca_drr_set_split": (C.c_int, [_I32]),
     "nca_drr_get_split": (C.c_int, []),
+    "nca_drr_backproject": (C.c_int, [C.POINTER(NcaGrid), _I32, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "nca_drr_set_backproject_runs": (C.c_int, [_I32]),
+    "nca_drr_get_backproject_runs": (C.c_int, []),
     "nca_drr_last_error": (C.c_char_p, []),
 }
 

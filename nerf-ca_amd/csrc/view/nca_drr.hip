@@ -1,7 +1,8 @@
 // nca_drr.hip -- cone-beam projection of voxel volumes (include/nerfca_hip.h, "drr"): line integrals of trilinearly interpolated f32
 // grids along f64 rays, pix = i0 - sum_s value(o + d z_s) dists_s, the quadrature of the renderer.  What turns a CT / phantom volume
-// into training projections (drr.volume_teacher) and an exported 4-D density grid back into images (drr.project_sequence).  Forward
-// only.  This translation unit keeps its own thread-local error message (nca_drr_last_error): it shares no state with nca_api.hip or
+// into training projections (drr.volume_teacher) and an exported 4-D density grid back into images (drr.project_sequence), and its
+// adjoint nca_drr_backproject, which scatters pixel gradients back onto the grid (the backward of drr.project_rays, what drr.fit_volumes
+// descends by).  This translation unit keeps its own thread-local error message (nca_drr_last_error): it shares no state with nca_api.hip or
 // nca_view.hip.
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -185,5 +186,184 @@ extern "C" int nca_drr_project(const NcaGrid* grid, const float* vol, int32_t n_
     }
     const hipError_t e = hipGetLastError();          // once, after the last group
     if (e != hipSuccess) return dfail(NCA_E_HIP, "nca_drr_project: %s", hipGetErrorString(e));
+    return NCA_OK;
+}
+
+// ---- back-projection: the adjoint of nca_drr_project in the volumes ---------------------------------------------------------------------
+constexpr int DRR_BACK_PARTS = 4;          // threads that share a ray: part j takes the j-th quarter of the depth steps
+constexpr int DRR_DEFAULT_BACK_RUNS = 1;   // the structure tools/drr_grad_bench.py measured as the faster one
+
+static std::atomic<int> g_drr_back_runs{DRR_DEFAULT_BACK_RUNS};
+
+extern "C" int nca_drr_set_backproject_runs(int32_t runs) {
+    if (runs != 0 && runs != 1) return dfail(NCA_E_INVALID, "nca_drr_set_backproject_runs: runs = %d is neither 0 nor 1", (int)runs);
+    g_drr_back_runs.store(runs);
+    return NCA_OK;
+}
+
+extern "C" int nca_drr_get_backproject_runs(void) { return g_drr_back_runs.load(); }
+
+// One thread per (ray, part) as in drr_kernel, but part j of the four marches the CONTIGUOUS steps [j ceil(S/4), (j+1) ceil(S/4)): there is no
+// cross-thread sum to fold here, the partition only puts four times the waves on the device, and contiguous steps keep a ray's consecutive
+// samples (which mostly share a cell) in one thread.  A wave is still 64 adjacent detector pixels at one depth step, so the nodes its 64 lanes
+// add into fall in a compact block of voxels.  A sample's indices and its eight weights are computed once and applied to all NV volumes.
+//
+// RUNS = false: one atomic add per (sample, neighbour, volume).
+// RUNS = true:  the thread keeps the 8 NV contributions of its current cell (i0a, i1a, i2a) in registers while consecutive samples stay in that
+//               cell, summing them in s order, and adds them to memory when the cell changes and after its last step.
+// Both add exactly the contributions of the definition; they differ in the order of a node's sum only.  Interior cells (all eight neighbours are
+// nodes) add unguarded, cells in the one-cell rim guard each neighbour, samples outside add nothing.  An early return is safe: no barrier.
+template <int NV, bool RUNS>
+__global__ void __launch_bounds__(DRR_BLOCK) drr_back_kernel(NcaGrid g, int64_t voxels, int64_t R, int32_t S, const double* __restrict__ origins,
+                                                             const double* __restrict__ dirs, const float* __restrict__ z, const double* __restrict__ dists,
+                                                             const double* __restrict__ g_pix, double* __restrict__ g_vol) {
+    constexpr int RAYS = DRR_BLOCK / DRR_BACK_PARTS;
+    const int slot = threadIdx.x % RAYS, part = threadIdx.x / RAYS;
+    const int64_t ray = (int64_t)blockIdx.x * RAYS + slot;
+    if (ray >= R) return;
+    const int32_t per = (S + DRR_BACK_PARTS - 1) / DRR_BACK_PARTS;          // the host refuses an S within 4 of INT32_MAX
+    const int64_t s_lo = (int64_t)part * per, s_hi = s_lo + per < S ? s_lo + per : S;
+    const double o0 = origins[3 * ray], o1 = origins[3 * ray + 1], o2 = origins[3 * ray + 2];
+    const double d0 = dirs[3 * ray], d1 = dirs[3 * ray + 1], d2 = dirs[3 * ray + 2];
+    const int32_t n0 = g.n[0], n1 = g.n[1], n2 = g.n[2];
+    const int64_t row = n2, slab = (int64_t)n1 * n2;
+    const int64_t off[8] = {0, 1, row, row + 1, slab, slab + 1, slab + row, slab + row + 1};          // neighbour k = 4 a + 2 b + c
+    double gp[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) gp[v] = g_pix[(int64_t)v * R + ray];
+
+    // the run of the current cell (RUNS only)
+    double acc[RUNS ? NV : 1][8];
+    int32_t c0 = 0, c1 = 0, c2 = 0;
+    bool open = false;
+    auto flush = [&]() {          // the cell (c0, c1, c2), each in [-1, n - 1]: add the run's sums to the neighbours that are nodes
+        const int64_t base = ((int64_t)c0 * n1 + c1) * n2 + c2;
+        const bool ok0[2] = {c0 >= 0, c0 + 1 < n0}, ok1[2] = {c1 >= 0, c1 + 1 < n1}, ok2[2] = {c2 >= 0, c2 + 1 < n2};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (ok0[k >> 2] && ok1[(k >> 1) & 1] && ok2[k & 1]) {
+#pragma unroll
+                for (int v = 0; v < (RUNS ? NV : 1); ++v) atomicAdd(g_vol + (int64_t)v * voxels + (base + off[k]), acc[v][k]);
+            }
+        }
+    };
+
+    for (int64_t s = s_lo; s < s_hi; ++s) {
+        const double zz = (double)z[s];
+        const double g0 = __dmul_rn(__dsub_rn(__dadd_rn(o0, __dmul_rn(d0, zz)), g.lo[0]), g.inv[0]);
+        const double g1 = __dmul_rn(__dsub_rn(__dadd_rn(o1, __dmul_rn(d1, zz)), g.lo[1]), g.inv[1]);
+        const double g2 = __dmul_rn(__dsub_rn(__dadd_rn(o2, __dmul_rn(d2, zz)), g.lo[2]), g.inv[2]);
+        // the forward's test: outside (-1, n) on any axis (or NaN) the sample read nothing, so it adds nothing
+        if (!(g0 > -1.0 && g0 < (double)n0 && g1 > -1.0 && g1 < (double)n1 && g2 > -1.0 && g2 < (double)n2)) continue;
+        const double fl0 = floor(g0), fl1 = floor(g1), fl2 = floor(g2);
+        const double f0 = __dsub_rn(g0, fl0), f1 = __dsub_rn(g1, fl1), f2 = __dsub_rn(g2, fl2);
+        const double x0[2] = {__dsub_rn(1.0, f0), f0}, x1[2] = {__dsub_rn(1.0, f1), f1}, x2[2] = {__dsub_rn(1.0, f2), f2};
+        const int32_t i0a = (int32_t)fl0, i1a = (int32_t)fl1, i2a = (int32_t)fl2;          // each in [-1, n - 1]
+        double w[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) w[k] = __dmul_rn(__dmul_rn(x0[k >> 2], x1[(k >> 1) & 1]), x2[k & 1]);          // (x0 x1) x2
+        const double ds = dists[s];
+        if constexpr (RUNS) {
+            if (!open || i0a != c0 || i1a != c1 || i2a != c2) {
+                if (open) flush();
+                c0 = i0a, c1 = i1a, c2 = i2a, open = true;
+#pragma unroll
+                for (int v = 0; v < NV; ++v) {
+                    const double t = -__dmul_rn(gp[v], ds);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) acc[v][k] = __dmul_rn(t, w[k]);
+                }
+            } else {
+#pragma unroll
+                for (int v = 0; v < NV; ++v) {
+                    const double t = -__dmul_rn(gp[v], ds);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) acc[v][k] = __dadd_rn(acc[v][k], __dmul_rn(t, w[k]));
+                }
+            }
+        } else {
+            const int64_t base = ((int64_t)i0a * n1 + i1a) * n2 + i2a;          // of neighbour (0,0,0); used only where that is valid
+            if (i0a >= 0 && i0a < n0 - 1 && i1a >= 0 && i1a < n1 - 1 && i2a >= 0 && i2a < n2 - 1) {
+#pragma unroll
+                for (int v = 0; v < NV; ++v) {
+                    const double t = -__dmul_rn(gp[v], ds);
+                    double* p = g_vol + (int64_t)v * voxels + base;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) atomicAdd(p + off[k], __dmul_rn(t, w[k]));
+                }
+            } else {
+                const bool ok0[2] = {i0a >= 0, i0a + 1 < n0}, ok1[2] = {i1a >= 0, i1a + 1 < n1}, ok2[2] = {i2a >= 0, i2a + 1 < n2};
+#pragma unroll
+                for (int v = 0; v < NV; ++v) {
+                    const double t = -__dmul_rn(gp[v], ds);
+                    double* p = g_vol + (int64_t)v * voxels;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k)
+                        if (ok0[k >> 2] && ok1[(k >> 1) & 1] && ok2[k & 1]) atomicAdd(p + (base + off[k]), __dmul_rn(t, w[k]));
+                }
+            }
+        }
+    }
+    if constexpr (RUNS) {
+        if (open) flush();
+    }
+}
+
+template <int NV>
+static void launch_back_group(bool runs, dim3 grid, hipStream_t st, const NcaGrid& g, int64_t voxels, int64_t R, int32_t S, const double* origins, const double* dirs,
+                              const float* z, const double* dists, const double* g_pix, double* g_vol) {
+    if (runs)
+        hipLaunchKernelGGL((drr_back_kernel<NV, true>), grid, dim3(DRR_BLOCK), 0, st, g, voxels, R, S, origins, dirs, z, dists, g_pix, g_vol);
+    else
+        hipLaunchKernelGGL((drr_back_kernel<NV, false>), grid, dim3(DRR_BLOCK), 0, st, g, voxels, R, S, origins, dirs, z, dists, g_pix, g_vol);
+}
+
+extern "C" int nca_drr_backproject(const NcaGrid* grid, int32_t n_vol, int64_t R, int32_t S, const double* origins, const double* dirs, const float* z,
+                                   const double* dists, const double* g_pix, double* g_vol, void* stream) {
+    if (!grid) return dfail(NCA_E_INVALID, "nca_drr_backproject: the grid descriptor is NULL");
+    if (!origins) return dfail(NCA_E_INVALID, "nca_drr_backproject: origins is NULL");
+    if (!dirs) return dfail(NCA_E_INVALID, "nca_drr_backproject: dirs is NULL");
+    if (!z) return dfail(NCA_E_INVALID, "nca_drr_backproject: z is NULL");
+    if (!dists) return dfail(NCA_E_INVALID, "nca_drr_backproject: dists is NULL");
+    if (!g_pix) return dfail(NCA_E_INVALID, "nca_drr_backproject: g_pix is NULL");
+    if (!g_vol) return dfail(NCA_E_INVALID, "nca_drr_backproject: g_vol is NULL");
+    if (n_vol <= 0) return dfail(NCA_E_INVALID, "nca_drr_backproject: n_vol = %d is not positive", (int)n_vol);
+    if (R <= 0) return dfail(NCA_E_INVALID, "nca_drr_backproject: R = %lld is not positive", (long long)R);
+    if (S <= 0) return dfail(NCA_E_INVALID, "nca_drr_backproject: S = %d is not positive", (int)S);
+    if (S > INT32_MAX - DRR_BACK_PARTS) return dfail(NCA_E_INVALID, "nca_drr_backproject: S = %d is more than one launch covers", (int)S);
+    const NcaGrid g = *grid;
+    if (g.reserved != 0) return dfail(NCA_E_INVALID, "nca_drr_backproject: reserved = %d is not 0", (int)g.reserved);
+    for (int a = 0; a < 3; ++a) {
+        if (g.n[a] < 2) return dfail(NCA_E_INVALID, "nca_drr_backproject: n[%d] = %d is less than 2 nodes", a, (int)g.n[a]);
+        if (!isfinite(g.lo[a])) return dfail(NCA_E_INVALID, "nca_drr_backproject: lo[%d] = %g is not finite", a, g.lo[a]);
+        if (!isfinite(g.inv[a])) return dfail(NCA_E_INVALID, "nca_drr_backproject: inv[%d] = %g is not finite", a, g.inv[a]);
+        if (!(g.inv[a] > 0.0)) return dfail(NCA_E_INVALID, "nca_drr_backproject: inv[%d] = %g is not positive", a, g.inv[a]);
+    }
+    // the bytes of all f64 gradient volumes must fit int64
+    const int64_t n01 = (int64_t)g.n[0] * g.n[1];
+    if (n01 > (INT64_MAX / 8 / n_vol) / g.n[2])
+        return dfail(NCA_E_INVALID, "nca_drr_backproject: %d volumes of %d x %d x %d voxels overflow int64", (int)n_vol, (int)g.n[0], (int)g.n[1], (int)g.n[2]);
+    const int64_t voxels = n01 * g.n[2];
+    if (R > INT64_MAX / 8 / n_vol) return dfail(NCA_E_INVALID, "nca_drr_backproject: R = %lld rays x %d volumes overflows int64", (long long)R, (int)n_vol);
+    const bool runs = g_drr_back_runs.load() != 0;
+    const int64_t rays_per_block = DRR_BLOCK / DRR_BACK_PARTS, blocks = (R + rays_per_block - 1) / rays_per_block;
+    if (blocks > 0x7fffffffLL) return dfail(NCA_E_INVALID, "nca_drr_backproject: R = %lld is more than one launch covers", (long long)R);
+    const dim3 grd((unsigned)blocks);
+    const hipStream_t st = (hipStream_t)stream;
+    for (int32_t v0 = 0; v0 < n_vol;) {          // groups of 8, 4, 2, 1 volumes, as in nca_drr_project
+        const int32_t left = n_vol - v0;
+        const int32_t nv = left >= DRR_MAX_GROUP ? DRR_MAX_GROUP : (left >= 4 ? 4 : (left >= 2 ? 2 : 1));
+        const double* gp = g_pix + (int64_t)v0 * R;
+        double* gv = g_vol + (int64_t)v0 * voxels;
+        switch (nv) {
+            case 8: launch_back_group<8>(runs, grd, st, g, voxels, R, S, origins, dirs, z, dists, gp, gv); break;
+            case 4: launch_back_group<4>(runs, grd, st, g, voxels, R, S, origins, dirs, z, dists, gp, gv); break;
+            case 2: launch_back_group<2>(runs, grd, st, g, voxels, R, S, origins, dirs, z, dists, gp, gv); break;
+            default: launch_back_group<1>(runs, grd, st, g, voxels, R, S, origins, dirs, z, dists, gp, gv); break;
+        }
+        v0 += nv;
+    }
+    const hipError_t e = hipGetLastError();          // once, after the last group
+    if (e != hipSuccess) return dfail(NCA_E_HIP, "nca_drr_backproject: %s", hipGetErrorString(e));
     return NCA_OK;
 }

@@ -12,12 +12,16 @@ interpolated f32 grid along the rays ``nca_view_rays`` generates, by the rendere
 
 A grid is ``export.density_volume``'s: ``linspace(lo, hi, n)`` nodes per axis, the volume ``[n0, n1, n2]`` with the last axis fastest;
 outside the grid the volume is 0.  There is no torch implementation behind these functions.
+
+``project_rays`` is differentiable in ``volumes`` (``nca_drr_backproject``, the adjoint kernel), and ``fit_volumes`` descends on a
+static volume and a stack of phase volumes until their projections match measured frames: the iterative voxel reconstruction a field
+is compared with, and the check of an exported grid against images.
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Callable, Optional, Sequence, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -51,13 +55,62 @@ def _default_dists(z: torch.Tensor) -> torch.Tensor:
     return _interval_lengths(z, torch.empty(0, dtype=torch.float64, device=z.device))
 
 
-@torch.no_grad()
+def _launch_project(volumes, o, d, z, dists, i0, desc):
+    """pix f64 [n_vol,R]: one nca_drr_project of checked, contiguous operands."""
+    n_vol = 1 if volumes.dim() == 3 else volumes.shape[0]
+    R, S = o.shape[0], z.shape[0]
+    pix = torch.empty((n_vol, R), dtype=torch.float64, device=volumes.device)
+    with torch.cuda.device(volumes.device):
+        _capi.check_drr(_capi.lib().nca_drr_project(C.byref(desc), _capi.ptr(volumes), n_vol, R, S, _capi.ptr(o), _capi.ptr(d), _capi.ptr(z),
+                                                    _capi.ptr(dists), float(i0), _capi.ptr(pix), _fused._stream()))
+    return pix
+
+
+class _ProjectRays(torch.autograd.Function):
+    """``project_rays`` with a gradient in ``volumes``: the forward is the same launch, the backward is ``nca_drr_backproject`` into a
+    zeroed f64 buffer, returned as f32 in the volumes' shape.  Rays, depths, interval lengths and ``i0`` get no gradient."""
+
+    @staticmethod
+    def forward(ctx, volumes, o, d, z, dists, i0, desc):
+        ctx.save_for_backward(o, d, z, dists)
+        ctx.desc, ctx.shape = desc, volumes.shape
+        return _launch_project(volumes.detach(), o, d, z, dists, i0, desc)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_pix):
+        o, d, z, dists = ctx.saved_tensors
+        shape = ctx.shape
+        dev = o.device
+        if g_pix.device != dev:
+            raise _capi.NcaError(f"project_rays backward: the pixel gradient lives on {g_pix.device}, the volumes on {dev}")
+        n_vol = 1 if len(shape) == 3 else shape[0]
+        R, S = o.shape[0], z.shape[0]
+        g_pix = g_pix.to(torch.float64).contiguous().view(n_vol, R)
+        g_vol = torch.zeros((n_vol, math.prod(shape[-3:])), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _capi.check_drr(_capi.lib().nca_drr_backproject(C.byref(ctx.desc), n_vol, R, S, _capi.ptr(o), _capi.ptr(d), _capi.ptr(z), _capi.ptr(dists),
+                                                            _capi.ptr(g_pix), _capi.ptr(g_vol), _fused._stream()))
+        return g_vol.to(torch.float32).reshape(shape), None, None, None, None, None, None
+
+
 def project_rays(volumes: torch.Tensor, origins: torch.Tensor, dirs: torch.Tensor, z: torch.Tensor, dists: Optional[torch.Tensor] = None, *,
                  i0: float, bounds: Bounds) -> torch.Tensor:
     """``i0 - sum_s volume(o + d z_s) dists_s`` of f32 ``volumes`` ``[n0,n1,n2]`` (returns f64 ``[R]``) or ``[n_vol,n0,n1,n2]``
     (returns f64 ``[n_vol,R]``; the volumes share one grid and are marched in one pass) along the rays ``origins`` / ``dirs``
     ``[R,3]`` (f64, or f32 widened) at the depths ``z`` ``[S]`` shared by all rays.  ``dists`` ``[S]`` defaults to
-    ``model_helpers._interval_lengths(z)``.  ``bounds`` places the grid (``grid_desc``)."""
+    ``model_helpers._interval_lengths(z)``.  ``bounds`` places the grid (``grid_desc``).
+
+    With grad mode on and ``volumes.requires_grad`` the result carries a gradient in ``volumes`` (f32, the volumes' shape; the adjoint
+    kernel sums in f64 atomics, so its last bits can differ from run to run).  Rays, ``z``, ``dists`` and ``i0`` get no gradient.  In
+    every other case nothing is recorded and the result is the plain launch's."""
+    if torch.is_grad_enabled() and isinstance(volumes, torch.Tensor) and volumes.requires_grad:
+        return _project_rays(volumes, origins, dirs, z, dists, i0, bounds, True)
+    with torch.no_grad():
+        return _project_rays(volumes, origins, dirs, z, dists, i0, bounds, False)
+
+
+def _project_rays(volumes, origins, dirs, z, dists, i0, bounds, differentiable):
     for t, what in ((volumes, "volumes"), (origins, "ray origins"), (dirs, "ray directions"), (z, "depth values")):
         _fused._require_cuda(t, what)
     dev = volumes.device
@@ -82,12 +135,7 @@ def project_rays(volumes: torch.Tensor, origins: torch.Tensor, dirs: torch.Tenso
     o = origins.detach().to(torch.float64).contiguous()
     d = dirs.detach().to(torch.float64).contiguous()
     desc = grid_desc(volumes.shape[-3:], bounds)
-    n_vol = 1 if volumes.dim() == 3 else volumes.shape[0]
-    R, S = o.shape[0], z.shape[0]
-    pix = torch.empty((n_vol, R), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check_drr(_capi.lib().nca_drr_project(C.byref(desc), _capi.ptr(volumes), n_vol, R, S, _capi.ptr(o), _capi.ptr(d), _capi.ptr(z),
-                                                    _capi.ptr(dists), float(i0), _capi.ptr(pix), _fused._stream()))
+    pix = _ProjectRays.apply(volumes, o, d, z, dists, float(i0), desc) if differentiable else _launch_project(volumes, o, d, z, dists, i0, desc)
     return pix[0] if volumes.dim() == 3 else pix
 
 
@@ -186,8 +234,103 @@ def volume_teacher(bounds: Bounds) -> Callable:
         if lo < 0:
             raise _capi.NcaError(f"volume_teacher: phase {int(lo)} is negative")
         phase = int(lo) % vol_dynamic.shape[0]          # the heart cycle is periodic: make_dataset's held-out image is phase 3 whatever n_phases
-        pix_s = project_rays(vol_static, origins, dirs, z, dists, i0=i_lo, bounds=bounds)
-        pix_d = project_rays(vol_dynamic[phase], origins, dirs, z, dists, i0=i_lo, bounds=bounds)
+        with torch.no_grad():          # a dataset is made of numbers: nothing is recorded, whatever the teacher volumes require
+            pix_s = project_rays(vol_static, origins, dirs, z, dists, i0=i_lo, bounds=bounds)
+            pix_d = project_rays(vol_dynamic[phase], origins, dirs, z, dists, i0=i_lo, bounds=bounds)
         return (pix_s + pix_d) - i_lo
 
     return render
+
+
+def fit_volumes(frames: Sequence[Tuple[float, float, int, torch.Tensor]], geo: dict, shape: Sequence[int], samples: int, *, bounds: Bounds = UNIT_BOUNDS,
+                n_phases: int, steps: int, lr: float = 1e-2, init: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, nonneg: bool = True,
+                chunk_rays: int = 65536, z: Optional[torch.Tensor] = None) -> dict:
+    """Voxel reconstruction from projections by gradient descent: fit a static volume ``[n0,n1,n2]`` and a dynamic stack
+    ``[n_phases,n0,n1,n2]`` (f32, nodes ``linspace(lo, hi, n)`` of ``bounds``) to ``frames``, a list of ``(theta, phi, phase, image)``
+    with ``image`` f32 ``[W,H]`` on the device in the log space the datasets hold (``I0 = geo["max_pixel_value"]``).
+
+    A frame's prediction is ``(A s + A d_phase) - I0`` in f64, composed as ``volume_teacher`` composes it, so a dataset made by that
+    hook is reproduced at loss 0.  Frames are grouped by view: per view and ray chunk a step makes one ``project_rays`` of the static
+    volume and ONE of all the phase volumes that view has.  The loss is the mean squared error over all pixels of all frames, the
+    optimiser ``torch.optim.Adam(lr)``; ``nonneg`` clamps both volumes at 0 after each step.  ``init`` is a pair of starting volumes
+    (default: zeros); ``z`` defaults to the un-jittered ``create_depth_values(near, far, samples)``.  Nothing is read back inside the
+    loop.  Returns ``{"static", "dynamic", "loss"}``: the fitted f32 volumes and the loss before each step as a list of floats.
+
+    Refused (``NcaError``): no frames, a phase outside ``[0, n_phases)``, an image that is not f32 ``[W,H]`` on the volumes' device."""
+    from .train.data_helpers import create_depth_values
+    frames = list(frames)
+    if not frames:
+        raise _capi.NcaError("fit_volumes: no frames to fit")
+    shape = tuple(int(n) for n in shape)
+    grid_desc(shape, bounds)          # refuses a bad grid before anything is allocated
+    n_phases, steps = int(n_phases), int(steps)
+    if n_phases < 1 or steps < 1:
+        raise _capi.NcaError(f"fit_volumes: n_phases = {n_phases} and steps = {steps} must be positive")
+    W, H = (int(v) for v in geo["nDetector"])
+    npix = W * H
+    first = frames[0][3]
+    if not isinstance(first, torch.Tensor):
+        raise _capi.NcaError("fit_volumes: a frame is (theta, phi, phase, image) with image a tensor")
+    _fused._require_cuda(first, "frame images")
+    dev = first.device
+    by_view = {}
+    for k, frame in enumerate(frames):
+        if len(frame) != 4:
+            raise _capi.NcaError(f"fit_volumes: frame {k} is not (theta, phi, phase, image)")
+        theta, phi, phase, image = frame
+        if int(phase) != phase or not 0 <= int(phase) < n_phases:
+            raise _capi.NcaError(f"fit_volumes: frame {k} has phase {phase}, outside [0, {n_phases})")
+        if not isinstance(image, torch.Tensor) or image.dtype != torch.float32 or tuple(image.shape) != (W, H):
+            raise _capi.NcaError(f"fit_volumes: the image of frame {k} is not float32 [{W},{H}]: got "
+                                 f"{getattr(image, 'dtype', type(image))} {tuple(getattr(image, 'shape', ()))}")
+        if image.device != dev:
+            raise _capi.NcaError(f"fit_volumes: the image of frame {k} lives on {image.device}, frame 0 on {dev}")
+        by_view.setdefault((float(theta), float(phi)), []).append((int(phase), image.detach().reshape(npix).to(torch.float64)))
+    if init is None:
+        static = torch.zeros(shape, dtype=torch.float32, device=dev)
+        dynamic = torch.zeros((n_phases,) + shape, dtype=torch.float32, device=dev)
+    else:
+        static, dynamic = (t.detach().to(device=dev, dtype=torch.float32).clone().contiguous() for t in init)
+        if tuple(static.shape) != shape or tuple(dynamic.shape) != (n_phases,) + shape:
+            raise _capi.NcaError(f"fit_volumes: init is (static {shape}, dynamic {(n_phases,) + shape}), got {tuple(static.shape)} and {tuple(dynamic.shape)}")
+    static.requires_grad_(True)
+    dynamic.requires_grad_(True)
+    if z is None:
+        z = create_depth_values(geo["near_thresh"], geo["far_thresh"], int(samples), dev)
+    z = z.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if z.dim() != 1:
+        raise _capi.NcaError("volume projection takes ONE depth vector [S] shared by all rays")
+    dists = _default_dists(z).to(torch.float64).contiguous()
+    i0 = float(torch.tensor(geo["max_pixel_value"], dtype=torch.float32))
+    plan = _export.chunk_plan(npix, int(chunk_rays))
+    # per view, once: the rays of every chunk, the rows of the dynamic stack the view's frames use, and the targets [F,npix] in f64
+    work: List[tuple] = []
+    with torch.cuda.device(dev), torch.no_grad():
+        for (theta, phi), items in by_view.items():
+            desc = _export.pack_view(geo, theta, phi)
+            rays = [_export._rays_of(desc, p0, n, dev, torch.float64) for p0, n in plan]
+            rows = torch.tensor([p for p, _ in items], dtype=torch.int64, device=dev)
+            work.append((rays, rows, torch.stack([img for _, img in items])))
+    total = float(len(frames) * npix)
+    opt = torch.optim.Adam([static, dynamic], lr=float(lr))
+    losses = torch.zeros(steps, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        for step in range(steps):
+            opt.zero_grad(set_to_none=True)
+            loss = torch.zeros((), dtype=torch.float64, device=dev)
+            for rays, rows, target in work:
+                stack = dynamic.index_select(0, rows)          # [F,n0,n1,n2]: the phases this view has, projected in one pass
+                for (p0, n), (o, d) in zip(plan, rays):
+                    pix_s = project_rays(static, o, d, z, dists, i0=i0, bounds=bounds)
+                    pix_d = project_rays(stack, o, d, z, dists, i0=i0, bounds=bounds)
+                    diff = ((pix_s[None] + pix_d) - i0) - target[:, p0:p0 + n]
+                    loss = loss + (diff * diff).sum()
+            loss = loss / total
+            loss.backward()
+            losses[step] = loss.detach()
+            opt.step()
+            if nonneg:
+                with torch.no_grad():
+                    static.clamp_(min=0)
+                    dynamic.clamp_(min=0)
+    return {"static": static.detach(), "dynamic": dynamic.detach(), "loss": losses.tolist()}
