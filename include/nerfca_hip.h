@@ -634,6 +634,38 @@ int nca_drr_get_backproject_runs(void);
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_drr_last_error(void);
 
+/* ---- vol: smoothed total variation of voxel volumes in space and along the heart phase (drr.total_variation / fit_volumes) ---------------
+ * The priors of the voxel reconstruction.  Purely additive to ABI 13.  Like the view and drr sections, these entry points keep their OWN
+ * per-thread message (the accessor below); a refused call launches nothing and reads no pointer; a launch failure is reported once.
+ *
+ * vol f32 [n_vol][n0][n1][n2] contiguous on one NcaGrid (lo is validated but unused), each value widened to f64; eps_s, eps_t > 0.  Every
+ * operation below is ONE rounded f64 operation in the order written (no contraction).
+ * Space, per volume and node i = (i0, i1, i2):
+ *     d_a(i) = (x[i + e_a] - x[i]) inv[a] for i_a < n_a - 1, 0 at the last node of axis a (forward differences, no wrap-around);
+ *     m(i) = sqrt(eps_s eps_s + ((d_0 d_0 + d_1 d_1) + d_2 d_2));   term(i) = m(i) - eps_s;   space = sum over volumes and nodes;
+ *     own = -((d_0(i) inv[0] + d_1(i) inv[1]) + d_2(i) inv[2]) / m(i);   back_a = (d_a(i - e_a) inv[a]) / m(i - e_a) for i_a > 0, else 0;
+ *     g_s(i) = ((own + back_0) + back_1) + back_2.
+ * Heart phase: the n_vol volumes of one call are one stack.  Pairs (p, p + 1), p = 0 .. n_vol - 2; with cyclic != 0 and n_vol >= 2 also
+ * (n_vol - 1, 0) (n_vol == 2 then carries its pair twice); n_vol == 1 has none.  Per pair and node:
+ *     t = x[p+1][i] - x[p][i];   mt = sqrt(eps_t eps_t + t t);   term = mt - eps_t;   time = sum over pairs and nodes;
+ *     g_t of x[p][i] = (-(t_p / mt_p)) + (t_{p-1} / mt_{p-1}), a pair that does not exist contributing 0.
+ * A flat stack has space = time = 0 exactly and a zero gradient.
+ * NCA_E_INVALID (the message names the value): a NULL pointer; n_vol <= 0; cyclic not 0 / 1; an eps that is not finite and positive; the
+ * grid refusals of nca_drr_project; more tiles (of 4 x 8 x 64 nodes) than one launch covers. */
+
+/* out f64 [2] on the device, ADDED INTO: out[0] += space, out[1] += time.  Only the order of the two sums is free: f64 block sums, then one
+ * f64 atomic add per block and term, so the last bits of the two values can differ from run to run. */
+int nca_vol_tv(const NcaGrid* grid, const float* vol, int32_t n_vol, double eps_s, double eps_t, int32_t cyclic, double* out, void* stream);
+
+/* g_vol f32 [n_vol][n0*n1*n2], WRITTEN: g_vol[v][i] = (float)(scale[0] g_s + scale[1] g_t), two rounded f64 products, one rounded f64 sum,
+ * one rounding to f32.  scale is f64 [2] ON THE DEVICE (a backward pass hands over its upstream gradients without a read-back).  Gathered:
+ * every node is written once by one thread, no atomics, the same bits on every run. */
+int nca_vol_tv_grad(const NcaGrid* grid, const float* vol, int32_t n_vol, double eps_s, double eps_t, int32_t cyclic, const double* scale,
+                    float* g_vol, void* stream);
+
+/* The message of the calling thread's last failed call of this section. */
+const char* nca_vol_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,9 @@ SYMBOLS = {
     "nca_drr_set_backproject_runs": (C.c_int, [_I32]),
     "nca_drr_get_backproject_runs": (C.c_int, []),
     "nca_drr_last_error": (C.c_char_p, []),
+    "nca_vol_tv": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, C.c_double, _I32, _P, _P]),
+    "nca_vol_tv_grad": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, C.c_double, _I32, _P, _P, _P]),
+    "nca_vol_last_error": (C.c_char_p, []),
 }
 
 
@@ -242,6 +245,13 @@ def check_drr(rc: int) -> int:
     """``check`` for the volume-projection entry points (nca_drr_*): they keep their own message."""
     if rc < 0:
         raise NcaError(f"libnerfca_hip: {lib().nca_drr_last_error().decode()} (code {rc})")
+    return rc
+
+
+def check_vol(rc: int) -> int:
+    """``check`` for the volume-prior entry points (nca_vol_*): they keep their own message."""
+    if rc < 0:
+        raise NcaError(f"libnerfca_hip: {lib().nca_vol_last_error().decode()} (code {rc})")
     return rc
 
 

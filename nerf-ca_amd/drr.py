@@ -15,7 +15,9 @@ outside the grid the volume is 0.  There is no torch implementation behind these
 
 ``project_rays`` is differentiable in ``volumes`` (``nca_drr_backproject``, the adjoint kernel), and ``fit_volumes`` descends on a
 static volume and a stack of phase volumes until their projections match measured frames: the iterative voxel reconstruction a field
-is compared with, and the check of an exported grid against images.
+is compared with, and the check of an exported grid against images.  ``total_variation`` (csrc/view/nca_voltv.hip) is the prior such a
+reconstruction carries when the views are few: the smoothed total variation of the volumes in space and between neighbouring heart phases,
+differentiable in the volumes; ``fit_volumes`` adds it to the data term with ``tv_space`` / ``tv_time``.
 """
 from __future__ import annotations
 
@@ -139,6 +141,79 @@ def _project_rays(volumes, origins, dirs, z, dists, i0, bounds, differentiable):
     return pix[0] if volumes.dim() == 3 else pix
 
 
+class _TotalVariation(torch.autograd.Function):
+    """``total_variation`` with a gradient in ``volumes``: the forward is one ``nca_vol_tv``, the backward one ``nca_vol_tv_grad`` whose device
+    ``scale`` holds the two upstream gradients times the normalisations -- nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, volumes, desc, eps_space, eps_time, cyclic):
+        ctx.save_for_backward(volumes)
+        ctx.args = (desc, eps_space, eps_time, cyclic)
+        return _launch_tv(volumes.detach(), desc, eps_space, eps_time, cyclic)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_space, g_time):
+        (volumes,) = ctx.saved_tensors
+        desc, eps_space, eps_time, cyclic = ctx.args
+        dev = volumes.device
+        if g_space.device != dev or g_time.device != dev:
+            raise _capi.NcaError(f"total_variation backward: the upstream gradients live on {g_space.device} and {g_time.device}, the volumes on {dev}")
+        n_vol, voxels, n_pairs = _tv_counts(volumes, cyclic)
+        scale = torch.stack([g_space.to(torch.float64).reshape(()) / float(n_vol * voxels),
+                             g_time.to(torch.float64).reshape(()) / float(n_pairs * voxels) if n_pairs else torch.zeros((), dtype=torch.float64, device=dev)])
+        g_vol = torch.empty_like(volumes)
+        with torch.cuda.device(dev):
+            _capi.check_vol(_capi.lib().nca_vol_tv_grad(C.byref(desc), _capi.ptr(volumes), n_vol, eps_space, eps_time, int(cyclic), _capi.ptr(scale),
+                                                        _capi.ptr(g_vol), _fused._stream()))
+        return g_vol, None, None, None, None
+
+
+def _tv_counts(volumes, cyclic):
+    """(n_vol, voxels, n_pairs) of a stack: pairs (p, p + 1), and (n_vol - 1, 0) when cyclic and n_vol >= 2."""
+    n_vol = 1 if volumes.dim() == 3 else volumes.shape[0]
+    return n_vol, math.prod(volumes.shape[-3:]), n_vol - 1 + (1 if cyclic and n_vol >= 2 else 0)
+
+
+def _launch_tv(volumes, desc, eps_space, eps_time, cyclic):
+    """(tv_space, tv_time) f64 0-d: one nca_vol_tv of checked, contiguous volumes into a zeroed pair, divided by the counts."""
+    n_vol, voxels, n_pairs = _tv_counts(volumes, cyclic)
+    sums = torch.zeros(2, dtype=torch.float64, device=volumes.device)
+    with torch.cuda.device(volumes.device):
+        _capi.check_vol(_capi.lib().nca_vol_tv(C.byref(desc), _capi.ptr(volumes), n_vol, eps_space, eps_time, int(cyclic), _capi.ptr(sums), _fused._stream()))
+    return sums[0] / float(n_vol * voxels), (sums[1] / float(n_pairs * voxels) if n_pairs else torch.zeros((), dtype=torch.float64, device=volumes.device))
+
+
+def total_variation(volumes: torch.Tensor, *, bounds: Bounds, eps_space: float = 1e-3, eps_time: float = 1e-3, cyclic: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Smoothed total variation of f32 ``volumes`` ``[n0,n1,n2]`` or ``[n_vol,n0,n1,n2]`` (contiguous, on the device, nodes
+    ``linspace(lo, hi, n)`` of ``bounds``), as two f64 0-d device tensors ``(tv_space, tv_time)``:
+
+    * ``tv_space``: the mean over volumes and nodes of ``sqrt(eps_space^2 + |forward differences / node spacing|^2) - eps_space``;
+    * ``tv_time``: the volumes are one stack of heart phases; the mean over pairs ``(p, p + 1)`` and nodes of
+      ``sqrt(eps_time^2 + (x[p+1] - x[p])^2) - eps_time``.  ``cyclic`` adds the pair ``(n_vol - 1, 0)`` of a periodic cycle (``n_vol >= 2``);
+      without pairs (one volume) it is exactly 0.
+
+    Means, so that a weight means the same at every resolution; a flat stack gives exactly ``(0, 0)``.  The definition, operation by
+    operation, is in include/nerfca_hip.h ("vol").  The sums are f64 atomics over blocks: their last bits can differ from run to run.
+
+    With grad mode on and ``volumes.requires_grad`` both results carry a gradient in ``volumes`` (f32, the volumes' shape, one gathered
+    kernel launch, the same bits on every run).  In every other case nothing is recorded."""
+    _fused._require_cuda(volumes, "volumes")
+    if volumes.dtype != torch.float32 or volumes.dim() not in (3, 4) or not volumes.is_contiguous() or volumes.numel() == 0:
+        raise _capi.NcaError(f"total_variation takes contiguous float32 volumes [n0,n1,n2] or [n_vol,n0,n1,n2], got {volumes.dtype} "
+                             f"{tuple(volumes.shape)}{'' if volumes.is_contiguous() else ' (not contiguous)'}")
+    eps_space, eps_time = float(eps_space), float(eps_time)
+    for eps, what in ((eps_space, "eps_space"), (eps_time, "eps_time")):
+        if not (math.isfinite(eps) and eps > 0):
+            raise _capi.NcaError(f"total_variation: {what} = {eps} is not finite and positive")
+    desc = grid_desc(volumes.shape[-3:], bounds)
+    cyclic = bool(cyclic)
+    if torch.is_grad_enabled() and volumes.requires_grad:
+        return _TotalVariation.apply(volumes, desc, eps_space, eps_time, cyclic)
+    with torch.no_grad():
+        return _launch_tv(volumes.detach(), desc, eps_space, eps_time, cyclic)
+
+
 @torch.no_grad()
 def project_sequence(sigma_static: torch.Tensor, sigma_dynamic: Optional[torch.Tensor], geo: dict, views: Sequence[Sequence[float]], samples: int, *,
                      bounds: Bounds = UNIT_BOUNDS, z: Optional[torch.Tensor] = None, chunk_rays: int = 65536, normalize: bool = False) -> dict:
@@ -244,7 +319,7 @@ def volume_teacher(bounds: Bounds) -> Callable:
 
 def fit_volumes(frames: Sequence[Tuple[float, float, int, torch.Tensor]], geo: dict, shape: Sequence[int], samples: int, *, bounds: Bounds = UNIT_BOUNDS,
                 n_phases: int, steps: int, lr: float = 1e-2, init: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, nonneg: bool = True,
-                chunk_rays: int = 65536, z: Optional[torch.Tensor] = None) -> dict:
+                chunk_rays: int = 65536, z: Optional[torch.Tensor] = None, tv_space: float = 0.0, tv_time: float = 0.0, tv_eps: float = 1e-3) -> dict:
     """Voxel reconstruction from projections by gradient descent: fit a static volume ``[n0,n1,n2]`` and a dynamic stack
     ``[n_phases,n0,n1,n2]`` (f32, nodes ``linspace(lo, hi, n)`` of ``bounds``) to ``frames``, a list of ``(theta, phi, phase, image)``
     with ``image`` f32 ``[W,H]`` on the device in the log space the datasets hold (``I0 = geo["max_pixel_value"]``).
@@ -256,7 +331,13 @@ def fit_volumes(frames: Sequence[Tuple[float, float, int, torch.Tensor]], geo: d
     (default: zeros); ``z`` defaults to the un-jittered ``create_depth_values(near, far, samples)``.  Nothing is read back inside the
     loop.  Returns ``{"static", "dynamic", "loss"}``: the fitted f32 volumes and the loss before each step as a list of floats.
 
-    Refused (``NcaError``): no frames, a phase outside ``[0, n_phases)``, an image that is not f32 ``[W,H]`` on the volumes' device."""
+    ``tv_space`` / ``tv_time`` > 0 add the priors of ``total_variation`` (``eps_space = eps_time = tv_eps``, ``cyclic=True``: the stack is one
+    periodic heart cycle): the objective is ``mse + tv_space (TVs(static) + TVs(dynamic)) + tv_time TVt(dynamic)``.  The result then also
+    holds ``"tv_space"`` and ``"tv_time"``, the unweighted ``TVs(static) + TVs(dynamic)`` and ``TVt(dynamic)`` before each step as lists of
+    floats; ``"loss"`` stays the data term.  With both weights 0 no prior kernel is launched and the result is as above.
+
+    Refused (``NcaError``): no frames, a phase outside ``[0, n_phases)``, an image that is not f32 ``[W,H]`` on the volumes' device, a
+    weight that is negative or not finite, a ``tv_eps`` that is not finite and positive."""
     from .train.data_helpers import create_depth_values
     frames = list(frames)
     if not frames:
@@ -266,6 +347,13 @@ def fit_volumes(frames: Sequence[Tuple[float, float, int, torch.Tensor]], geo: d
     n_phases, steps = int(n_phases), int(steps)
     if n_phases < 1 or steps < 1:
         raise _capi.NcaError(f"fit_volumes: n_phases = {n_phases} and steps = {steps} must be positive")
+    tv_space, tv_time, tv_eps = float(tv_space), float(tv_time), float(tv_eps)
+    for w, what in ((tv_space, "tv_space"), (tv_time, "tv_time")):
+        if not (math.isfinite(w) and w >= 0):
+            raise _capi.NcaError(f"fit_volumes: {what} = {w} is not a finite weight >= 0")
+    if not (math.isfinite(tv_eps) and tv_eps > 0):
+        raise _capi.NcaError(f"fit_volumes: tv_eps = {tv_eps} is not finite and positive")
+    priors = tv_space > 0 or tv_time > 0
     W, H = (int(v) for v in geo["nDetector"])
     npix = W * H
     first = frames[0][3]
@@ -314,6 +402,7 @@ def fit_volumes(frames: Sequence[Tuple[float, float, int, torch.Tensor]], geo: d
     total = float(len(frames) * npix)
     opt = torch.optim.Adam([static, dynamic], lr=float(lr))
     losses = torch.zeros(steps, dtype=torch.float64, device=dev)
+    tvs = torch.zeros((2, steps), dtype=torch.float64, device=dev) if priors else None
     with torch.cuda.device(dev):
         for step in range(steps):
             opt.zero_grad(set_to_none=True)
@@ -326,11 +415,20 @@ def fit_volumes(frames: Sequence[Tuple[float, float, int, torch.Tensor]], geo: d
                     diff = ((pix_s[None] + pix_d) - i0) - target[:, p0:p0 + n]
                     loss = loss + (diff * diff).sum()
             loss = loss / total
-            loss.backward()
             losses[step] = loss.detach()
+            if priors:
+                space_s, _ = total_variation(static, bounds=bounds, eps_space=tv_eps, eps_time=tv_eps)
+                space_d, time_d = total_variation(dynamic, bounds=bounds, eps_space=tv_eps, eps_time=tv_eps, cyclic=True)
+                space = space_s + space_d
+                tvs[0, step], tvs[1, step] = space.detach(), time_d.detach()
+                loss = loss + tv_space * space + tv_time * time_d
+            loss.backward()
             opt.step()
             if nonneg:
                 with torch.no_grad():
                     static.clamp_(min=0)
                     dynamic.clamp_(min=0)
-    return {"static": static.detach(), "dynamic": dynamic.detach(), "loss": losses.tolist()}
+    out = {"static": static.detach(), "dynamic": dynamic.detach(), "loss": losses.tolist()}
+    if priors:
+        out["tv_space"], out["tv_time"] = tvs.tolist()
+    return out

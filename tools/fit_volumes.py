@@ -9,10 +9,11 @@ composite frames, one per (view, phase), in the log space of the datasets; its g
 manifest without phases (a static-only run) is read as phase 0 of every view.  --shape n0,n1,n2 and --bounds x0,x1,y0,y1,z0,z1 place the
 grid to fit (linspace(lo, hi, n) nodes per axis; --bounds defaults to the manifest's, else to +-1).  --samples defaults to the manifest's.
 --n-phases is the length of the dynamic stack (default: the largest phase of the manifest + 1).  Views with a C-arm roll (larm != 0) are
-refused: drr.fit_volumes takes (theta, phi).
+refused: drr.fit_volumes takes (theta, phi).  --tv-space / --tv-time weigh the total-variation priors in space and between neighbouring
+heart phases (drr.total_variation; 0, the default, fits the data term alone), --tv-eps is their smoothing constant.
 
 Writes static.npy [n0,n1,n2] and dynamic.npy [n_phases,n0,n1,n2] (f32), the files tools/project_volumes.py reads back with --static /
---dynamic, and fit.json (the loss before each step).
+--dynamic, and fit.json (the loss before each step; with a prior on, also the two unweighted total variations before each step).
 """
 import argparse
 import json
@@ -55,6 +56,9 @@ def parser():
     ap.add_argument("--lr", type=float, default=1e-2)
     ap.add_argument("--allow-negative", action="store_true", help="do not clamp the volumes at 0 after each step")
     ap.add_argument("--chunk-rays", type=int, default=65536)
+    ap.add_argument("--tv-space", type=float, default=0.0, help="weight of the spatial total variation of the static volume and the stack")
+    ap.add_argument("--tv-time", type=float, default=0.0, help="weight of the total variation between neighbouring phases of the cyclic stack")
+    ap.add_argument("--tv-eps", type=float, default=1e-3, help="smoothing constant of both total variations")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--out", required=True, help="output directory")
     return ap
@@ -108,13 +112,16 @@ def main(argv=None):
     bounds = args.bounds or info["bounds"] or ((-1.0, 1.0),) * 3
     n_phases = info["n_phases"] if args.n_phases is None else args.n_phases
     out = drr.fit_volumes([(t, p, ph, torch.from_numpy(img).to(dev)) for t, p, ph, img in frames], geo, args.shape, samples, bounds=bounds,
-                          n_phases=n_phases, steps=args.steps, lr=args.lr, nonneg=not args.allow_negative, chunk_rays=args.chunk_rays)
+                          n_phases=n_phases, steps=args.steps, lr=args.lr, nonneg=not args.allow_negative, chunk_rays=args.chunk_rays,
+                          tv_space=args.tv_space, tv_time=args.tv_time, tv_eps=args.tv_eps)
     os.makedirs(args.out, exist_ok=True)
     np.save(os.path.join(args.out, "static.npy"), out["static"].cpu().numpy())
     np.save(os.path.join(args.out, "dynamic.npy"), out["dynamic"].cpu().numpy())
+    record = {"frames": len(frames), "shape": list(args.shape), "bounds": [list(b) for b in bounds], "samples": samples, "n_phases": n_phases,
+              "steps": args.steps, "lr": args.lr, "tv_space_weight": args.tv_space, "tv_time_weight": args.tv_time, "tv_eps": args.tv_eps, "loss": out["loss"]}
+    record.update({k: out[k] for k in ("tv_space", "tv_time") if k in out})
     with open(os.path.join(args.out, "fit.json"), "w") as f:
-        json.dump({"frames": len(frames), "shape": list(args.shape), "bounds": [list(b) for b in bounds], "samples": samples, "n_phases": n_phases,
-                   "steps": args.steps, "lr": args.lr, "loss": out["loss"]}, f, indent=1)
+        json.dump(record, f, indent=1)
     print(json.dumps({"out": args.out, "files": ["dynamic", "static"], "first_loss": out["loss"][0], "last_loss": out["loss"][-1]}))
 
 
