@@ -666,6 +666,45 @@ int nca_vol_tv_grad(const NcaGrid* grid, const float* vol, int32_t n_vol, double
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_vol_last_error(void);
 
+/* ---- phantom: a procedural 4-D phantom rasterised into voxel grids (phantom.voxelize / make_phantom) -----------------------------------------
+ * Soft ellipsoids (a static thorax, additive) and tapered capsules (vessels, a maximum) per heart phase -> out f32 [n_phase][n0][n1][n2] on
+ * one NcaGrid, the grids nca_drr_project, nca_vol_tv and export take.  Purely additive to ABI 13.  Like the view, drr and vol sections,
+ * these entry points keep their OWN per-thread message (the accessor below); a refused call launches nothing and reads no pointer; a launch
+ * failure is reported once.
+ *
+ * Every operation below is ONE rounded f64 operation in the order written (no contraction).
+ * Node i = (i_0, i_1, i_2):   h_a = 1 / inv_a, formed once per axis;   x_a = lo_a + (double)i_a h_a.
+ * Ellipsoid row f64 [14] = centre c[3], matrix A[9] (row-major), soft width w > 0, density rho:
+ *     u = x - c;   q_k = (A_k0 u_0 + A_k1 u_1) + A_k2 u_2;   r = sqrt((q_0 q_0 + q_1 q_1) + q_2 q_2);
+ *     cov = min(max(0.5 + (1 - r) / w, 0), 1);   background = ((0 + rho_0 cov_0) + rho_1 cov_1) + ... in row order (additive: a lung is a
+ *     negative rho).
+ * Segment row f64 [8] = endpoints a[3], b[3], radii ra, rb >= 0 (a tapered capsule); edge > 0 is one length for the call:
+ *     e = b - a;   ee = (e_0 e_0 + e_1 e_1) + e_2 e_2;   q = x - a;   qe = (q_0 e_0 + q_1 e_1) + q_2 e_2;
+ *     t = min(max(qe / ee, 0), 1), and t = 0 when ee == 0 (a sphere);   c_k = q_k - t e_k;   d = sqrt((c_0 c_0 + c_1 c_1) + c_2 c_2);
+ *     r = ra + t (rb - ra);   cov = min(max(0.5 + (r - d) / edge, 0), 1);   vessels = rho_v max_n cov_n, the maximum starting from 0.
+ *     A maximum, not a sum: consecutive segments of a polyline and branch junctions do not double-count, and the order of the rows cannot
+ *     change a bit.
+ * out[p][i] = (float)(background_p(i) + vessels_p(i)).  Both tables are per phase, on the device: ell f64 [n_phase][n_ell][14] and seg f64
+ * [n_phase][n_seg][8]; either count may be 0, not both.  What the tables hold is the caller's responsibility (phantom.voxelize checks it).
+ * Every node of every phase is written exactly once by one thread: no atomics, the same bits on every run.  Segments are staged through LDS
+ * in batches of NCA_PHANTOM_SEG_BATCH.  `grid` is a host pointer.
+ * NCA_E_INVALID (the message names the value): a NULL grid or out; n_phase <= 0; a negative count, or both counts 0; a NULL table whose
+ * count is positive; edge not finite and positive; rho_v not finite; the grid refusals of nca_drr_project; more tiles (of 4 x 8 x 64 nodes,
+ * times n_phase) than one launch covers. */
+enum { NCA_PHANTOM_SEG_BATCH = 512 };
+int nca_phantom_voxelize(const NcaGrid* grid, int32_t n_phase, int32_t n_ell, const double* ell, int32_t n_seg, const double* seg,
+                         double rho_v, double edge, float* out, void* stream);
+
+/* Culling (process-wide): 1 = a staged segment whose box (its endpoints' box grown by max(ra, rb) + edge / 2, padded by a relative 2^-20)
+ * misses the tile's box is dropped before any node of the tile evaluates it; 0 = every node evaluates every segment.  cov is exactly 0 at
+ * every node that far from a segment, so both give the same bits.  The default is the faster of the two as measured by
+ * tools/phantom_bench.py; the other stays for that tool and the tests.  set: NCA_E_INVALID for any other value. */
+int nca_phantom_set_cull(int32_t on);
+int nca_phantom_get_cull(void);
+
+/* The message of the calling thread's last failed call of this section. */
+const char* nca_phantom_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,5 +6,6 @@ hyphen).  ``model/`` and ``train/`` mirror the reference's packages of the same 
 from . import _capi  # noqa: F401
 from .fused import render_rays, eval_points, set_precision  # noqa: F401
 from . import drr  # noqa: F401
+from . import phantom  # noqa: F401
 
-__all__ = ["render_rays", "eval_points", "set_precision", "drr"]
+__all__ = ["render_rays", "eval_points", "set_precision", "drr", "phantom"]

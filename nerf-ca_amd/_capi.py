@@ -206,6 +206,10 @@ SYMBOLS = {
     "nca_vol_tv": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, C.c_double, _I32, _P, _P]),
     "nca_vol_tv_grad": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, C.c_double, _I32, _P, _P, _P]),
     "nca_vol_last_error": (C.c_char_p, []),
+    "nca_phantom_voxelize": (C.c_int, [C.POINTER(NcaGrid), _I32, _I32, _P, _I32, _P, C.c_double, C.c_double, _P, _P]),
+    "nca_phantom_set_cull": (C.c_int, [_I32]),
+    "nca_phantom_get_cull": (C.c_int, []),
+    "nca_phantom_last_error": (C.c_char_p, []),
 }
 
 
@@ -252,6 +256,13 @@ def check_vol(rc: int) -> int:
     """``check`` for the volume-prior entry points (nca_vol_*): they keep their own message."""
     if rc < 0:
         raise NcaError(f"libnerfca_hip: {lib().nca_vol_last_error().decode()} (code {rc})")
+    return rc
+
+
+def check_phantom(rc: int) -> int:
+    """``check`` for the phantom entry points (nca_phantom_*): they keep their own message."""
+    if rc < 0:
+        raise NcaError(f"libnerfca_hip: {lib().nca_phantom_last_error().decode()} (code {rc})")
     return rc
 
 

@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""What the total-variation priors do to a sparse-view voxel fit against known truth, on the procedural phantom (nerfca_amd.phantom).
+
+Per grid size n (64 and 128 nodes per axis), with P = 10 heart phases at synthetic.xcat_geometry:
+
+  1. make_phantom((n, n, n), 10): the truth, a static thorax and a beating coronary tree.
+  2. drr.project_sequence of the truth through the four training views (-30,30), (-30,-30), (60,-30), (60,30) at every phase: 40 frames.
+     The frames come from the grid that is fitted, so a volume pair with loss 0 exists: what is measured is what four views leave open.
+  3. drr.fit_volumes from zeros, with the priors off and with tv_space / tv_time on (a small table of weights).
+  4. phantom.volume_errors of the fitted volumes against the truth: RMSE of the static volume, of the dynamic stack and of their sum
+     (the split between the two is not determined by the frames, their sum is what a ray sees), the Dice coefficient of the vessel mask
+     (dynamic > a quarter and > a twentieth of the vessel density), the largest fitted dynamic value, and the PSNR of the held-out view
+     (-5, 40) over all phases (peak = the range of the true images).
+
+Also the reprojection distance of the phantom per grid size: project_sequence of the phantom rasterised at n against the same phantom
+rasterised at 256 nodes per axis, over the four training views and all phases.
+
+These numbers are recorded and gated nowhere.
+
+    python3 tools/phantom_study.py [--out profiles/phantom_study.txt]
+"""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+PHASES = 10
+HELD_OUT = (-5.0, 40.0)
+WEIGHTS = [(0.0, 0.0), (1e-5, 0.0), (1e-4, 0.0), (0.0, 1e-1), (0.0, 1.0), (0.0, 10.0), (1e-5, 1e-1), (1e-5, 1.0), (1e-4, 1.0)]          # (tv_space, tv_time)
+FINE = 256
+
+
+def psnr(pred, truth):
+    mse = float(((pred.double() - truth.double()) ** 2).mean())
+    peak = float(truth.max() - truth.min())
+    return math.inf if mse == 0 else 10.0 * math.log10(peak * peak / mse)
+
+
+def study(dev, side, n_det, samples, steps, lr, weights):
+    from nerfca_amd import drr, phantom, synthetic
+    geo = synthetic.xcat_geometry(n_det)
+    ph = phantom.make_phantom((side,) * 3, PHASES, geo, device=dev)
+    bounds, static, dynamic = ph["bounds"], ph["static"], ph["dynamic"]
+    views = [tuple(float(a) for a in v) for v in synthetic.TRAIN_VIEWS]
+    train = drr.project_sequence(static, dynamic, geo, views, samples, bounds=bounds)["pred"]
+    held = drr.project_sequence(static, dynamic, geo, [HELD_OUT], samples, bounds=bounds)["pred"]
+    frames = [(theta, phi, p, train[v, p].contiguous()) for v, (theta, phi) in enumerate(views) for p in range(PHASES)]
+    threshold = 0.25 * phantom.RHO_VESSEL
+    rows = []
+    for tv_space, tv_time in weights:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fit = drr.fit_volumes(frames, geo, (side,) * 3, samples, bounds=bounds, n_phases=PHASES, steps=steps, lr=lr, tv_space=tv_space, tv_time=tv_time)
+        torch.cuda.synchronize()
+        seconds = time.perf_counter() - t0
+        e_s = phantom.volume_errors(fit["static"], static)
+        e_d = phantom.volume_errors(fit["dynamic"], dynamic, threshold)
+        e_low = phantom.volume_errors(fit["dynamic"], dynamic, 0.2 * threshold)
+        e_sum = phantom.volume_errors(fit["static"][None] + fit["dynamic"], static[None] + dynamic)
+        again = drr.project_sequence(fit["static"], fit["dynamic"], geo, [HELD_OUT], samples, bounds=bounds)["pred"]
+        rows.append({"volume": side, "tv_space": tv_space, "tv_time": tv_time, "steps": steps, "lr": lr, "fit_seconds": round(seconds, 2),
+                     "loss_first": fit["loss"][0], "loss_last": fit["loss"][-1], "rmse_static": e_s["rmse"], "rmse_dynamic": e_d["rmse"],
+                     "rmse_sum": e_sum["rmse"], "dice_vessels": e_d["dice"], "dice_vessels_low": e_low["dice"], "dynamic_max": float(fit["dynamic"].max()), "truth_dynamic_max": float(dynamic.max()), "psnr_held_out": psnr(again, held)})
+        print(json.dumps(rows[-1]), flush=True)
+    return rows, (geo, views, samples, train)
+
+
+def reprojection(dev, sides, n_det, samples):
+    """Distance of the frames of the phantom rasterised at each side from those of the phantom rasterised at FINE nodes per axis."""
+    from nerfca_amd import drr, phantom, synthetic
+    geo = synthetic.xcat_geometry(n_det)
+    views = [tuple(float(a) for a in v) for v in synthetic.TRAIN_VIEWS]
+    frames = {}
+    for side in tuple(sides) + (FINE,):
+        ph = phantom.make_phantom((side,) * 3, PHASES, geo, device=dev)
+        frames[side] = drr.project_sequence(ph["static"], ph["dynamic"], geo, views, samples, bounds=ph["bounds"])
+        del ph
+        torch.cuda.empty_cache()
+    rows = []
+    for side in sides:
+        rec = {"volume": side, "against": FINE}
+        for k in ("pred", "pred_static", "pred_dynamic"):
+            a, b = frames[side][k].double(), frames[FINE][k].double()
+            rec[k] = {"max_abs": float((a - b).abs().max()), "rmse": float(torch.sqrt(((a - b) ** 2).mean())), "psnr": psnr(a, b)}
+        rows.append(rec)
+        print(json.dumps(rec), flush=True)
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None, help="also write the report to this file")
+    ap.add_argument("--sides", default="64,128", help="grid sizes, comma separated")
+    ap.add_argument("--n-det", type=int, default=128)
+    ap.add_argument("--samples", type=int, default=192)
+    ap.add_argument("--steps", type=int, default=300)
+    ap.add_argument("--lr", type=float, default=0.05)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("phantom_study needs the GPU")
+    dev = torch.device("cuda:0")
+    sides = tuple(int(s) for s in args.sides.split(","))
+    fits = []
+    for side in sides:
+        fits += study(dev, side, args.n_det, args.samples, args.steps, args.lr, WEIGHTS)[0]
+        torch.cuda.empty_cache()
+    rep = reprojection(dev, sides, args.n_det, args.samples)
+    table = [f"fit_volumes on the phantom, P = {PHASES}, 4 training views of {args.n_det}^2 pixels x {args.samples} samples, {args.steps} Adam steps at lr {args.lr}, from zeros",
+             "volume  tv_space  tv_time   loss first -> last        rmse static  rmse dynamic  rmse sum   Dice >rho/4  Dice >rho/20  dynamic max (truth)  PSNR held-out (-5,40)   seconds"]
+    for r in fits:
+        table.append(f"{r['volume']:>4}^3  {r['tv_space']:<8g}  {r['tv_time']:<7g}   {r['loss_first']:.3e} -> {r['loss_last']:.3e}   {r['rmse_static']:>10.4f}   {r['rmse_dynamic']:>10.4f}   "
+                     f"{r['rmse_sum']:>8.4f}   {r['dice_vessels']:>10.4f}   {r['dice_vessels_low']:>10.4f}   {r['dynamic_max']:>8.3f} ({r['truth_dynamic_max']:.3f})   {r['psnr_held_out']:>12.2f} dB          {r['fit_seconds']:>7.1f}")
+    table.append(f"reprojection distance: the frames of the phantom rasterised at n^3 against those of the phantom at {FINE}^3 (4 views x {PHASES} phases)")
+    for r in rep:
+        table.append(f"{r['volume']:>4}^3   " + "   ".join(f"{k}: max {r[k]['max_abs']:.4e} rmse {r[k]['rmse']:.4e} PSNR {r[k]['psnr']:.2f} dB" for k in ("pred", "pred_static", "pred_dynamic")))
+    print("\n".join(table))
+    if args.out:
+        with open(args.out, "w") as f:
+            for r in fits + rep:
+                f.write(json.dumps(r) + "\n")
+            f.write("\n".join(table) + "\n")
+
+
+if __name__ == "__main__":
+    main()
