@@ -705,6 +705,56 @@ int nca_phantom_get_cull(void);
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_phantom_last_error(void);
 
+/* ---- ssim: structural similarity of image stacks and its gradient (metrics.ssim / compare_sequences, ssim_weight of drr.fit_volumes) --------
+ * The SSIM of Wang et al. of N image pairs with a separable window, in f64, and the gradient of its sum in the prediction.  Purely additive
+ * to ABI 13.  Like the view, drr, vol and phantom sections, these entry points keep their OWN per-thread message (the accessor below); a
+ * refused call launches nothing and reads no device pointer; a launch failure is reported once.
+ *
+ * x (prediction), y (truth): f32 [N][H][W] contiguous on the device.  range: f64 [N] ON THE DEVICE.  win: HOST f64 [K], K odd,
+ * 1 <= K <= NCA_SSIM_MAX_WIN, H >= K, W >= K: any weights (the library never calls exp; metrics.gaussian_window makes Wang's window and
+ * hands its bits over).  k1, k2 finite and positive.  Every operation below is ONE rounded f64 operation in the order written (the
+ * kernels spell each one out: nothing leans on a contraction flag).
+ * Per image n:   L = range[n];   C1 = (k1 L)(k1 L);   C2 = (k2 L)(k2 L).  An L that is not finite and positive gives NaN at every position
+ *     of that image (value, map and gradient); it is not checked on the host.
+ * Per pixel, five fields widened to f64: x, y, xx = x x, yy = y y, xy = x y (products of two f32 values: exact in f64).
+ * Statistics at the Hv x Wv = (H - K + 1) x (W - K + 1) window positions (i, j), separable, no padding, for each field v:
+ *     r_v(i, j) = (..((win[0] v(i, j)) + win[1] v(i, j + 1)) + ..) + win[K-1] v(i, j + K - 1)          rows i = 0 .. H - 1
+ *     m_v(i, j) = (..((win[0] r_v(i, j)) + win[1] r_v(i + 1, j)) + ..) + win[K-1] r_v(i + K - 1, j)
+ *     mx = m_x, my = m_y;   sxx = m_xx - mx mx;   syy = m_yy - my my;   sxy = m_xy - mx my;
+ *     a1 = 2 (mx my) + C1;   a2 = 2 sxy + C2;   b1 = (mx mx + my my) + C1;   b2 = (sxx + syy) + C2;   D = b1 b2;   S = (a1 a2) / D.
+ * x == y makes a1 == b1 and a2 == b2 bit for bit: S is exactly 1.
+ * Gradient of sum_p S_p in x (the window moments as variables: d mx = w dx, d m_xx = 2 w x dx, d m_xy = w y dx), per position:
+ *     P = ((2 my) (a2 - a1)) / D + (((2 mx) S) (b1 - b2)) / D;   Q = -((2 S) / b2);   R = (2 a1) / D;
+ * per pixel (i, j) of the H x W image, with F[M](i, j) = sum_{a,b} win[a] win[b] M(i - a, j - b) formed separably:
+ *     f_M(i', j) = sum over b = 0 .. K - 1, increasing, of win[b] M(i', j - b), only the terms with 0 <= j - b < Wv: the first of them
+ *                  starts the sum, the others are added in turn (a term outside is SKIPPED, not added as a zero);   rows i' = 0 .. Hv - 1
+ *     F[M](i, j) = sum over a = 0 .. K - 1, increasing, of win[a] f_M(i - a, j), only the terms with 0 <= i - a < Hv, in the same way
+ *                  (every pixel has at least one term in each pass);
+ *     g(i, j) = (float)(scale[n] ((F[P] + x F[Q]) + y F[R])),   x and y the pixel's own values widened.
+ * (tests/test_ssim_cpu.py holds these formulas to torch autograd of the conv2d expression in f64: nothing had to be corrected.)
+ * NCA_E_INVALID (the message names the value): a NULL pointer (map may be NULL); N, H or W <= 0; K even or outside [1, NCA_SSIM_MAX_WIN];
+ * H < K or W < K; a window entry that is not finite; a k that is not finite and positive; N H W beyond what int64 byte offsets carry; more
+ * than 2^24 tiles (of 16 x 32 pixels, all images together: 2^32 threads, what one launch covers).  NCA_E_WORKSPACE: work is NULL or work_bytes is below the query's answer. */
+enum { NCA_SSIM_MAX_WIN = 11 };
+
+/* sum f64 [N] on the device, ADDED INTO: sum[n] += sum over the Hv Wv positions of S.  Only the order of the sum is free: f64 block sums,
+ * then one f64 atomic add per block, so the last bits can differ from run to run.  map, when not NULL: f32 [N][Hv][Wv], WRITTEN,
+ * map = (float)S, every position once. */
+int nca_ssim(int32_t N, int32_t H, int32_t W, const float* x, const float* y, const double* range, int32_t K, const double* win, double k1,
+             double k2, double* sum, float* map, void* stream);
+
+/* The gradient runs as two kernels: the first writes P, Q, R as three f64 maps [3][N][Hv][Wv] into `work`, the second gathers them.  The
+ * query returns those bytes (24 N Hv Wv), and 0 for sizes the entry point refuses. */
+size_t nca_ssim_grad_workspace(int32_t N, int32_t H, int32_t W, int32_t K);
+
+/* g_x f32 [N][H][W], WRITTEN: every pixel once by one thread.  Gathered, no atomics, the same bits on every run.  scale is f64 [N] ON THE
+ * DEVICE (a backward pass hands over its upstream gradients without a read-back). */
+int nca_ssim_grad(int32_t N, int32_t H, int32_t W, const float* x, const float* y, const double* range, int32_t K, const double* win, double k1,
+                  double k2, const double* scale, float* g_x, void* work, size_t work_bytes, void* stream);
+
+/* The message of the calling thread's last failed call of this section. */
+const char* nca_ssim_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -210,6 +210,10 @@ SYMBOLS = {
     "nca_phantom_set_cull": (C.c_int, [_I32]),
     "nca_phantom_get_cull": (C.c_int, []),
     "nca_phantom_last_error": (C.c_char_p, []),
+    "nca_ssim": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _I32, C.POINTER(C.c_double), C.c_double, C.c_double, _P, _P, _P]),
+    "nca_ssim_grad_workspace": (C.c_size_t, [_I32, _I32, _I32, _I32]),
+    "nca_ssim_grad": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _I32, C.POINTER(C.c_double), C.c_double, C.c_double, _P, _P, _P, C.c_size_t, _P]),
+    "nca_ssim_last_error": (C.c_char_p, []),
 }
 
 
@@ -263,6 +267,13 @@ def check_phantom(rc: int) -> int:
     """``check`` for the phantom entry points (nca_phantom_*): they keep their own message."""
     if rc < 0:
         raise NcaError(f"libnerfca_hip: {lib().nca_phantom_last_error().decode()} (code {rc})")
+    return rc
+
+
+def check_ssim(rc: int) -> int:
+    """``check`` for the image-similarity entry points (nca_ssim*): they keep their own message."""
+    if rc < 0:
+        raise NcaError(f"libnerfca_hip: {lib().nca_ssim_last_error().decode()} (code {rc})")
     return rc
 
 

@@ -17,7 +17,8 @@ outside the grid the volume is 0.  There is no torch implementation behind these
 static volume and a stack of phase volumes until their projections match measured frames: the iterative voxel reconstruction a field
 is compared with, and the check of an exported grid against images.  ``total_variation`` (csrc/view/nca_voltv.hip) is the prior such a
 reconstruction carries when the views are few: the smoothed total variation of the volumes in space and between neighbouring heart phases,
-differentiable in the volumes; ``fit_volumes`` adds it to the data term with ``tv_space`` / ``tv_time``.
+differentiable in the volumes; ``fit_volumes`` adds it to the data term with ``tv_space`` / ``tv_time``, and a structural term
+(``metrics.ssim``) with ``ssim_weight``.
 """
 from __future__ import annotations
 
@@ -30,6 +31,7 @@ import torch
 from . import _capi
 from . import export as _export
 from . import fused as _fused
+from . import metrics as _metrics
 
 Bounds = Tuple[Tuple[float, float], ...]
 UNIT_BOUNDS: Bounds = ((-1.0, 1.0),) * 3
@@ -319,7 +321,8 @@ def volume_teacher(bounds: Bounds) -> Callable:
 
 def fit_volumes(frames: Sequence[Tuple[float, float, int, torch.Tensor]], geo: dict, shape: Sequence[int], samples: int, *, bounds: Bounds = UNIT_BOUNDS,
                 n_phases: int, steps: int, lr: float = 1e-2, init: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, nonneg: bool = True,
-                chunk_rays: int = 65536, z: Optional[torch.Tensor] = None, tv_space: float = 0.0, tv_time: float = 0.0, tv_eps: float = 1e-3) -> dict:
+                chunk_rays: int = 65536, z: Optional[torch.Tensor] = None, tv_space: float = 0.0, tv_time: float = 0.0, tv_eps: float = 1e-3,
+                ssim_weight: float = 0.0, ssim_win: int = 11) -> dict:
     """Voxel reconstruction from projections by gradient descent: fit a static volume ``[n0,n1,n2]`` and a dynamic stack
     ``[n_phases,n0,n1,n2]`` (f32, nodes ``linspace(lo, hi, n)`` of ``bounds``) to ``frames``, a list of ``(theta, phi, phase, image)``
     with ``image`` f32 ``[W,H]`` on the device in the log space the datasets hold (``I0 = geo["max_pixel_value"]``).
@@ -336,8 +339,16 @@ def fit_volumes(frames: Sequence[Tuple[float, float, int, torch.Tensor]], geo: d
     holds ``"tv_space"`` and ``"tv_time"``, the unweighted ``TVs(static) + TVs(dynamic)`` and ``TVt(dynamic)`` before each step as lists of
     floats; ``"loss"`` stays the data term.  With both weights 0 no prior kernel is launched and the result is as above.
 
+    ``ssim_weight`` > 0 adds a structural term (``metrics.ssim``, window ``ssim_win``): the objective gains
+    ``ssim_weight (1 - mean over frames of SSIM(prediction, image))``.  A view's ray chunks are concatenated into whole f32 ``[W,H]``
+    predictions before the call; the range of a frame is ``max - min`` of its image, formed once before the loop.  The result then also holds
+    ``"ssim"``, the unweighted mean SSIM before each step as a list of floats.  With weight 0 nothing of it is launched and the keys and bits
+    of the result are as without the argument.
+
     Refused (``NcaError``): no frames, a phase outside ``[0, n_phases)``, an image that is not f32 ``[W,H]`` on the volumes' device, a
-    weight that is negative or not finite, a ``tv_eps`` that is not finite and positive."""
+    weight that is negative or not finite, a ``tv_eps`` that is not finite and positive, with ``ssim_weight`` > 0 an ``ssim_win`` that is
+    not odd, above 11 or larger than the detector, and with ``ssim_weight`` > 0 a frame that is constant (its range is 0, for which SSIM is
+    NaN and would turn the whole objective into NaN; checked once before the loop, the one read-back the term costs)."""
     from .train.data_helpers import create_depth_values
     frames = list(frames)
     if not frames:
@@ -354,8 +365,18 @@ def fit_volumes(frames: Sequence[Tuple[float, float, int, torch.Tensor]], geo: d
     if not (math.isfinite(tv_eps) and tv_eps > 0):
         raise _capi.NcaError(f"fit_volumes: tv_eps = {tv_eps} is not finite and positive")
     priors = tv_space > 0 or tv_time > 0
+    ssim_weight = float(ssim_weight)
+    if not (math.isfinite(ssim_weight) and ssim_weight >= 0):
+        raise _capi.NcaError(f"fit_volumes: ssim_weight = {ssim_weight} is not a finite weight >= 0")
+    structural = ssim_weight > 0
     W, H = (int(v) for v in geo["nDetector"])
     npix = W * H
+    if structural:
+        if int(ssim_win) != ssim_win or not 1 <= int(ssim_win) <= _metrics.MAX_WIN or int(ssim_win) % 2 == 0:
+            raise _capi.NcaError(f"fit_volumes: ssim_win = {ssim_win} is not an odd window length in [1, {_metrics.MAX_WIN}]")
+        ssim_win = int(ssim_win)
+        if ssim_win > min(W, H):
+            raise _capi.NcaError(f"fit_volumes: ssim_win = {ssim_win} is larger than the detector, {W} x {H}")
     first = frames[0][3]
     if not isinstance(first, torch.Tensor):
         raise _capi.NcaError("fit_volumes: a frame is (theta, phi, phase, image) with image a tensor")
@@ -398,24 +419,48 @@ def fit_volumes(frames: Sequence[Tuple[float, float, int, torch.Tensor]], geo: d
             desc = _export.pack_view(geo, theta, phi)
             rays = [_export._rays_of(desc, p0, n, dev, torch.float64) for p0, n in plan]
             rows = torch.tensor([p for p, _ in items], dtype=torch.int64, device=dev)
-            work.append((rays, rows, torch.stack([img for _, img in items])))
+            target = torch.stack([img for _, img in items])
+            if structural:          # the f32 images and their ranges, once
+                images = target.to(torch.float32).reshape(-1, W, H)
+                work.append((rays, rows, target, images, images.amax(dim=(-2, -1)).double() - images.amin(dim=(-2, -1)).double()))
+            else:
+                work.append((rays, rows, target))
+    if structural:          # a constant image has range 0, for which SSIM is NaN: refused here, once, before the loop
+        flat = torch.cat([w[4] for w in work])
+        if not bool(((flat > 0) & torch.isfinite(flat)).all()):
+            raise _capi.NcaError(f"fit_volumes: ssim_weight > 0 needs frames whose max - min is finite and positive; {int((~((flat > 0) & torch.isfinite(flat))).sum())} "
+                                 f"of the {len(frames)} frames are constant or not finite")
     total = float(len(frames) * npix)
     opt = torch.optim.Adam([static, dynamic], lr=float(lr))
     losses = torch.zeros(steps, dtype=torch.float64, device=dev)
     tvs = torch.zeros((2, steps), dtype=torch.float64, device=dev) if priors else None
+    ssims = torch.zeros(steps, dtype=torch.float64, device=dev) if structural else None
     with torch.cuda.device(dev):
         for step in range(steps):
             opt.zero_grad(set_to_none=True)
             loss = torch.zeros((), dtype=torch.float64, device=dev)
-            for rays, rows, target in work:
+            similarity = torch.zeros((), dtype=torch.float64, device=dev) if structural else None
+            for rays, rows, target, *whole in work:
                 stack = dynamic.index_select(0, rows)          # [F,n0,n1,n2]: the phases this view has, projected in one pass
+                chunks = []
                 for (p0, n), (o, d) in zip(plan, rays):
                     pix_s = project_rays(static, o, d, z, dists, i0=i0, bounds=bounds)
                     pix_d = project_rays(stack, o, d, z, dists, i0=i0, bounds=bounds)
-                    diff = ((pix_s[None] + pix_d) - i0) - target[:, p0:p0 + n]
+                    pred = (pix_s[None] + pix_d) - i0
+                    diff = pred - target[:, p0:p0 + n]
                     loss = loss + (diff * diff).sum()
+                    if structural:
+                        chunks.append(pred)
+                if structural:
+                    images, ranges = whole
+                    frames_pred = (chunks[0] if len(chunks) == 1 else torch.cat(chunks, dim=1)).to(torch.float32).reshape(-1, W, H)
+                    similarity = similarity + _metrics.ssim(frames_pred, images, data_range=ranges, win_size=ssim_win).sum()
             loss = loss / total
             losses[step] = loss.detach()
+            if structural:
+                similarity = similarity / float(len(frames))
+                ssims[step] = similarity.detach()
+                loss = loss + ssim_weight * (1.0 - similarity)
             if priors:
                 space_s, _ = total_variation(static, bounds=bounds, eps_space=tv_eps, eps_time=tv_eps)
                 space_d, time_d = total_variation(dynamic, bounds=bounds, eps_space=tv_eps, eps_time=tv_eps, cyclic=True)
@@ -431,4 +476,6 @@ def fit_volumes(frames: Sequence[Tuple[float, float, int, torch.Tensor]], geo: d
     out = {"static": static.detach(), "dynamic": dynamic.detach(), "loss": losses.tolist()}
     if priors:
         out["tv_space"], out["tv_time"] = tvs.tolist()
+    if structural:
+        out["ssim"] = ssims.tolist()
     return out

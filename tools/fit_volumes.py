@@ -10,10 +10,13 @@ manifest without phases (a static-only run) is read as phase 0 of every view.  -
 grid to fit (linspace(lo, hi, n) nodes per axis; --bounds defaults to the manifest's, else to +-1).  --samples defaults to the manifest's.
 --n-phases is the length of the dynamic stack (default: the largest phase of the manifest + 1).  Views with a C-arm roll (larm != 0) are
 refused: drr.fit_volumes takes (theta, phi).  --tv-space / --tv-time weigh the total-variation priors in space and between neighbouring
-heart phases (drr.total_variation; 0, the default, fits the data term alone), --tv-eps is their smoothing constant.
+heart phases (drr.total_variation; 0, the default, fits the data term alone), --tv-eps is their smoothing constant.  --ssim-weight adds
+ssim_weight (1 - mean SSIM of the predicted frames) to the objective (metrics.ssim; 0, the default, launches nothing of it), --ssim-win
+is its window length (odd, at most 11, no larger than the detector).
 
 Writes static.npy [n0,n1,n2] and dynamic.npy [n_phases,n0,n1,n2] (f32), the files tools/project_volumes.py reads back with --static /
---dynamic, and fit.json (the loss before each step; with a prior on, also the two unweighted total variations before each step).
+--dynamic, and fit.json (the loss before each step; with a prior on, also the two unweighted total variations before each step; with --ssim-weight, also the
+mean SSIM before each step).
 """
 import argparse
 import json
@@ -59,6 +62,8 @@ def parser():
     ap.add_argument("--tv-space", type=float, default=0.0, help="weight of the spatial total variation of the static volume and the stack")
     ap.add_argument("--tv-time", type=float, default=0.0, help="weight of the total variation between neighbouring phases of the cyclic stack")
     ap.add_argument("--tv-eps", type=float, default=1e-3, help="smoothing constant of both total variations")
+    ap.add_argument("--ssim-weight", type=float, default=0.0, help="weight of 1 - mean SSIM of the predicted frames")
+    ap.add_argument("--ssim-win", type=int, default=11, help="window length of the SSIM term (odd, at most 11)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--out", required=True, help="output directory")
     return ap
@@ -113,13 +118,15 @@ def main(argv=None):
     n_phases = info["n_phases"] if args.n_phases is None else args.n_phases
     out = drr.fit_volumes([(t, p, ph, torch.from_numpy(img).to(dev)) for t, p, ph, img in frames], geo, args.shape, samples, bounds=bounds,
                           n_phases=n_phases, steps=args.steps, lr=args.lr, nonneg=not args.allow_negative, chunk_rays=args.chunk_rays,
-                          tv_space=args.tv_space, tv_time=args.tv_time, tv_eps=args.tv_eps)
+                          tv_space=args.tv_space, tv_time=args.tv_time, tv_eps=args.tv_eps, ssim_weight=args.ssim_weight, ssim_win=args.ssim_win)
     os.makedirs(args.out, exist_ok=True)
     np.save(os.path.join(args.out, "static.npy"), out["static"].cpu().numpy())
     np.save(os.path.join(args.out, "dynamic.npy"), out["dynamic"].cpu().numpy())
     record = {"frames": len(frames), "shape": list(args.shape), "bounds": [list(b) for b in bounds], "samples": samples, "n_phases": n_phases,
               "steps": args.steps, "lr": args.lr, "tv_space_weight": args.tv_space, "tv_time_weight": args.tv_time, "tv_eps": args.tv_eps, "loss": out["loss"]}
-    record.update({k: out[k] for k in ("tv_space", "tv_time") if k in out})
+    if args.ssim_weight > 0:
+        record.update({"ssim_weight": args.ssim_weight, "ssim_win": args.ssim_win})
+    record.update({k: out[k] for k in ("tv_space", "tv_time", "ssim") if k in out})
     with open(os.path.join(args.out, "fit.json"), "w") as f:
         json.dump(record, f, indent=1)
     print(json.dumps({"out": args.out, "files": ["dynamic", "static"], "first_loss": out["loss"][0], "last_loss": out["loss"][-1]}))

@@ -10,7 +10,12 @@ Per grid size n (64 and 128 nodes per axis), with P = 10 heart phases at synthet
   4. phantom.volume_errors of the fitted volumes against the truth: RMSE of the static volume, of the dynamic stack and of their sum
      (the split between the two is not determined by the frames, their sum is what a ray sees), the Dice coefficient of the vessel mask
      (dynamic > a quarter and > a twentieth of the vessel density), the largest fitted dynamic value, and the PSNR of the held-out view
-     (-5, 40) over all phases (peak = the range of the true images).
+     (-5, 40) over all phases (peak = the range of the true images), and the mean SSIM of the same held-out frames (metrics.ssim, window 11,
+     the range of each true frame).
+
+--ssim-weight W[,W..] adds, per grid size and weight, a fit with the structural term alone (ssim_weight = W) and one with it next to the
+spatial prior (tv_space 1e-5, the best PSNR row of the table at 64 nodes): whether a structural loss moves the vessel figures.  Without
+the option the rows are the table of total-variation weights alone.
 
 Also the reprojection distance of the phantom per grid size: project_sequence of the phantom rasterised at n against the same phantom
 rasterised at 256 nodes per axis, over the four training views and all phases.
@@ -43,8 +48,13 @@ def psnr(pred, truth):
     return math.inf if mse == 0 else 10.0 * math.log10(peak * peak / mse)
 
 
+def ssim_rows(ssim_weights):
+    """(tv_space, tv_time, ssim_weight) of the rows --ssim-weight adds."""
+    return [(tv_space, 0.0, w) for w in ssim_weights for tv_space in (0.0, 1e-5)]
+
+
 def study(dev, side, n_det, samples, steps, lr, weights):
-    from nerfca_amd import drr, phantom, synthetic
+    from nerfca_amd import drr, metrics, phantom, synthetic
     geo = synthetic.xcat_geometry(n_det)
     ph = phantom.make_phantom((side,) * 3, PHASES, geo, device=dev)
     bounds, static, dynamic = ph["bounds"], ph["static"], ph["dynamic"]
@@ -54,10 +64,13 @@ def study(dev, side, n_det, samples, steps, lr, weights):
     frames = [(theta, phi, p, train[v, p].contiguous()) for v, (theta, phi) in enumerate(views) for p in range(PHASES)]
     threshold = 0.25 * phantom.RHO_VESSEL
     rows = []
-    for tv_space, tv_time in weights:
+    held_range = held.amax(dim=(-2, -1)).double() - held.amin(dim=(-2, -1)).double()
+    for tv_space, tv_time, *rest in weights:
+        ssim_weight = rest[0] if rest else 0.0
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        fit = drr.fit_volumes(frames, geo, (side,) * 3, samples, bounds=bounds, n_phases=PHASES, steps=steps, lr=lr, tv_space=tv_space, tv_time=tv_time)
+        fit = drr.fit_volumes(frames, geo, (side,) * 3, samples, bounds=bounds, n_phases=PHASES, steps=steps, lr=lr, tv_space=tv_space, tv_time=tv_time,
+                              ssim_weight=ssim_weight)
         torch.cuda.synchronize()
         seconds = time.perf_counter() - t0
         e_s = phantom.volume_errors(fit["static"], static)
@@ -67,7 +80,10 @@ def study(dev, side, n_det, samples, steps, lr, weights):
         again = drr.project_sequence(fit["static"], fit["dynamic"], geo, [HELD_OUT], samples, bounds=bounds)["pred"]
         rows.append({"volume": side, "tv_space": tv_space, "tv_time": tv_time, "steps": steps, "lr": lr, "fit_seconds": round(seconds, 2),
                      "loss_first": fit["loss"][0], "loss_last": fit["loss"][-1], "rmse_static": e_s["rmse"], "rmse_dynamic": e_d["rmse"],
-                     "rmse_sum": e_sum["rmse"], "dice_vessels": e_d["dice"], "dice_vessels_low": e_low["dice"], "dynamic_max": float(fit["dynamic"].max()), "truth_dynamic_max": float(dynamic.max()), "psnr_held_out": psnr(again, held)})
+                     "rmse_sum": e_sum["rmse"], "dice_vessels": e_d["dice"], "dice_vessels_low": e_low["dice"], "dynamic_max": float(fit["dynamic"].max()), "truth_dynamic_max": float(dynamic.max()), "psnr_held_out": psnr(again, held),
+                     "ssim_weight": ssim_weight, "ssim_held_out": float(metrics.ssim(again, held, data_range=held_range).mean())})
+        if "ssim" in fit:
+            rows[-1].update({"ssim_train_first": fit["ssim"][0], "ssim_train_last": fit["ssim"][-1]})
         print(json.dumps(rows[-1]), flush=True)
     return rows, (geo, views, samples, train)
 
@@ -102,21 +118,23 @@ def main():
     ap.add_argument("--samples", type=int, default=192)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--lr", type=float, default=0.05)
+    ap.add_argument("--ssim-weight", default="", help="comma separated weights of the structural term: adds rows (default: none)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("phantom_study needs the GPU")
     dev = torch.device("cuda:0")
     sides = tuple(int(s) for s in args.sides.split(","))
+    ssim_weights = [float(w) for w in args.ssim_weight.split(",") if w.strip()]
     fits = []
     for side in sides:
-        fits += study(dev, side, args.n_det, args.samples, args.steps, args.lr, WEIGHTS)[0]
+        fits += study(dev, side, args.n_det, args.samples, args.steps, args.lr, WEIGHTS + ssim_rows(ssim_weights))[0]
         torch.cuda.empty_cache()
     rep = reprojection(dev, sides, args.n_det, args.samples)
     table = [f"fit_volumes on the phantom, P = {PHASES}, 4 training views of {args.n_det}^2 pixels x {args.samples} samples, {args.steps} Adam steps at lr {args.lr}, from zeros",
-             "volume  tv_space  tv_time   loss first -> last        rmse static  rmse dynamic  rmse sum   Dice >rho/4  Dice >rho/20  dynamic max (truth)  PSNR held-out (-5,40)   seconds"]
+             "volume  tv_space  tv_time   loss first -> last        rmse static  rmse dynamic  rmse sum   Dice >rho/4  Dice >rho/20  dynamic max (truth)  PSNR held-out (-5,40)   seconds   ssim_weight  SSIM held-out"]
     for r in fits:
         table.append(f"{r['volume']:>4}^3  {r['tv_space']:<8g}  {r['tv_time']:<7g}   {r['loss_first']:.3e} -> {r['loss_last']:.3e}   {r['rmse_static']:>10.4f}   {r['rmse_dynamic']:>10.4f}   "
-                     f"{r['rmse_sum']:>8.4f}   {r['dice_vessels']:>10.4f}   {r['dice_vessels_low']:>10.4f}   {r['dynamic_max']:>8.3f} ({r['truth_dynamic_max']:.3f})   {r['psnr_held_out']:>12.2f} dB          {r['fit_seconds']:>7.1f}")
+                     f"{r['rmse_sum']:>8.4f}   {r['dice_vessels']:>10.4f}   {r['dice_vessels_low']:>10.4f}   {r['dynamic_max']:>8.3f} ({r['truth_dynamic_max']:.3f})   {r['psnr_held_out']:>12.2f} dB          {r['fit_seconds']:>7.1f}   {r['ssim_weight']:<11g}  {r['ssim_held_out']:.4f}")
     table.append(f"reprojection distance: the frames of the phantom rasterised at n^3 against those of the phantom at {FINE}^3 (4 views x {PHASES} phases)")
     for r in rep:
         table.append(f"{r['volume']:>4}^3   " + "   ".join(f"{k}: max {r[k]['max_abs']:.4e} rmse {r[k]['rmse']:.4e} PSNR {r[k]['psnr']:.2f} dB" for k in ("pred", "pred_static", "pred_dynamic")))
