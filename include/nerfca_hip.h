@@ -755,6 +755,43 @@ int nca_ssim_grad(int32_t N, int32_t H, int32_t W, const float* x, const float* 
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_ssim_last_error(void);
 
+/* ---- edt: the exact Euclidean distance transform of thresholded voxel stacks (metrics.distance_transform / mask_distances /
+ *      centreline_coverage) -----------------------------------------------------------------------------------------------------------------
+ * The distance, in world units, from every node of a voxel grid to the nearest node whose value is above (or, inverted, not above) a
+ * threshold.  Purely additive to ABI 13.  Like the view, drr, vol, phantom and ssim sections, these entry points keep their OWN per-thread
+ * message (the accessor below); a refused call launches nothing and reads no device pointer; a launch failure is reported once.
+ *
+ * vol f32 [n_vol][n0][n1][n2] contiguous on one NcaGrid (lo is validated but unused).  `grid` is a host pointer.  Every operation below is
+ * ONE rounded f64 operation in the order written (the kernels spell each one out: nothing leans on a contraction flag).
+ *     h_a = 1 / inv_a;   w_a = h_a h_a, formed once per axis on the host in f64.
+ * Node j of volume v is a FEATURE iff ((double)vol[v][j] > threshold) != (invert != 0).  A NaN value is not > threshold: it is a feature
+ * only under invert.  A value equal to the threshold is not > threshold.
+ * For node i and feature j of the same volume, with the integer offsets d_a = i_a - j_a, their squares formed in int64 and converted
+ * exactly:
+ *     q(i, j) = w_0 (double)(d_0 d_0) + (w_1 (double)(d_1 d_1) + w_2 (double)(d_2 d_2));
+ *     out[v][i] = (float)sqrt(min over the features j of volume v of q(i, j)).
+ * A volume without a feature gives +inf at every node; a feature node gets exactly 0.  Every node of every volume is written exactly once
+ * by one thread: no atomics, the same bits on every run, and the result of a volume does not depend on n_vol or on its neighbours in the
+ * stack.
+ * The minimum over all features is the definition; the kernels form it separably -- g = the integer distance to the nearest feature of
+ * the row (axis 2), b = min_j1 (w_1 d_1^2 + w_2 g^2), out = sqrt(min_j0 (w_0 d_0^2 + b)) -- which gives the same bits: rounding is monotone
+ * and every term is non-negative, so the minimum of the rounded sums is the rounded sum with the minimum (tests/test_edt_cpu.py holds the two
+ * forms to each other bit for bit).  For the same reason a search outward from the node's own index stops at the first w_a d_a^2 that is
+ * not below the best value so far.
+ * The workspace holds b as f64 and g as int32 for every node: 12 bytes per node, rounded up to a multiple of 256.  The query returns it, and
+ * 0 for arguments the entry point refuses.
+ * NCA_E_INVALID (the message names the value): a NULL grid, vol or out; n_vol <= 0; invert not 0 / 1; a threshold that is NaN; the grid
+ * refusals of nca_drr_project; more than 2^24 workgroups in one of the three launches (rows / 4, or tiles of 16 lines: 2^32 threads, what
+ * one launch covers).  NCA_E_UNSUPPORTED: an axis longer than NCA_EDT_MAX_AXIS (a line tile of 16 x n_a f64 values is staged in the 64 KiB
+ * of LDS a workgroup may take).  NCA_E_WORKSPACE: work is NULL or work_bytes is below the query's answer. */
+enum { NCA_EDT_MAX_AXIS = 512 };
+size_t nca_vol_edt_workspace(const NcaGrid* grid, int32_t n_vol);
+int nca_vol_edt(const NcaGrid* grid, const float* vol, int32_t n_vol, double threshold, int32_t invert, float* out, void* work, size_t work_bytes,
+                void* stream);
+
+/* The message of the calling thread's last failed call of this section. */
+const char* nca_edt_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -214,6 +214,9 @@ SYMBOLS = {
     "nca_ssim_grad_workspace": (C.c_size_t, [_I32, _I32, _I32, _I32]),
     "nca_ssim_grad": (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _I32, C.POINTER(C.c_double), C.c_double, C.c_double, _P, _P, _P, C.c_size_t, _P]),
     "nca_ssim_last_error": (C.c_char_p, []),
+    "nca_vol_edt_workspace": (C.c_size_t, [C.POINTER(NcaGrid), _I32]),
+    "nca_vol_edt": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, _I32, _P, _P, C.c_size_t, _P]),
+    "nca_edt_last_error": (C.c_char_p, []),
 }
 
 
@@ -274,6 +277,13 @@ def check_ssim(rc: int) -> int:
     """``check`` for the image-similarity entry points (nca_ssim*): they keep their own message."""
     if rc < 0:
         raise NcaError(f"libnerfca_hip: {lib().nca_ssim_last_error().decode()} (code {rc})")
+    return rc
+
+
+def check_edt(rc: int) -> int:
+    """``check`` for the distance-transform entry points (nca_vol_edt*): they keep their own message."""
+    if rc < 0:
+        raise NcaError(f"libnerfca_hip: {lib().nca_edt_last_error().decode()} (code {rc})")
     return rc
 
 

@@ -1,10 +1,17 @@
-"""Comparing image stacks on the device: PSNR and the structural similarity of Wang et al. (csrc/view/nca_ssim.hip).
+"""Comparing image stacks and voxel stacks on the device: PSNR and the structural similarity of Wang et al. (csrc/view/nca_ssim.hip), and
+the exact Euclidean distance transform with the vessel distances built on it (csrc/view/nca_edt.hip).
 
 NeRF-CA reports its 2-D results as PSNR and SSIM.  ``ssim`` is one pass over the two stacks in f64 (``nca_ssim``): Gaussian-windowed
 means, variances and the covariance at every window position that lies inside the image (no padding), combined as include/nerfca_hip.h
 ("ssim") writes it, and averaged per image.  It is differentiable in the prediction (``nca_ssim_grad``: gathered, the same
 bits on every run), so ``1 - ssim`` serves as a loss; ``drr.fit_volumes`` takes it with ``ssim_weight``.  ``compare_sequences`` sets the
 stacks of ``export.render_sequence`` / ``drr.project_sequence`` side by side.  There is no torch implementation behind ``ssim``.
+
+In 3-D, ``distance_transform`` is the exact distance from every node of a voxel stack to the nearest node above a threshold
+(``nca_vol_edt``; include/nerfca_hip.h, "edt").  ``mask_distances`` (mean, Hausdorff and percentile distances between two thresholded
+stacks) and ``centreline_coverage`` (the share of a known centreline that lies within a tolerance of a thresholded stack) are torch
+reductions over two such maps: measures that stay graded where the Dice coefficient of thin vessels is 0.  There is no torch
+implementation behind ``distance_transform``.
 """
 from __future__ import annotations
 
@@ -187,3 +194,174 @@ def compare_sequences(pred: dict, truth: dict, *, data_range: Optional[Union[flo
     if not out:
         raise _capi.NcaError("compare_sequences: the two dicts share no image stack of one shape")
     return out
+
+
+# ----------------------------------------------------------------------------- distances in 3-D
+MAX_AXIS = 512          # NCA_EDT_MAX_AXIS
+
+
+def _grid_desc(shape, bounds):
+    from . import drr          # (drr imports this module for its structural term)
+    return drr.grid_desc(shape, bounds)
+
+
+def _check_volume(vol, who, what="vol"):
+    if not isinstance(vol, torch.Tensor):
+        raise _capi.NcaError(f"{who}: {what} is not a tensor")
+    _fused._require_cuda(vol, what)
+    if vol.dtype != torch.float32:
+        raise _capi.NcaError(f"{who} takes float32 volumes, got {vol.dtype}")
+    if vol.dim() < 3 or vol.numel() == 0:
+        raise _capi.NcaError(f"{who} takes a stack [..., n0, n1, n2], got {tuple(vol.shape)}")
+
+
+@torch.no_grad()
+def distance_transform(vol: torch.Tensor, bounds, *, threshold: float, inside: bool = False) -> torch.Tensor:
+    """The exact Euclidean distance transform of a thresholded f32 stack ``vol`` ``[..., n0, n1, n2]`` on the device, as an f32 tensor of
+    the same shape: the grid is ``drr.grid_desc(vol.shape[-3:], bounds)`` and distances are in its world units (anisotropic spacings are
+    honoured).  ``inside=False``: the distance from every node to the nearest node with ``vol > threshold`` (0 on the mask).
+    ``inside=True``: the distance to the nearest node that is NOT ``> threshold`` -- what
+    ``scipy.ndimage.distance_transform_edt(vol > threshold, sampling=h)`` returns.  A NaN value is not ``> threshold``.  A volume of the
+    stack with no such node is ``+inf`` everywhere; every volume is transformed on its own.
+
+    One ``nca_vol_edt`` (three launches; its definition, operation by operation, is in include/nerfca_hip.h, "edt"): the same bits on
+    every run.  Not differentiable: it runs under ``no_grad`` and the result is detached.  An axis longer than 512 nodes is refused."""
+    _check_volume(vol, "distance_transform")
+    threshold = float(threshold)
+    if math.isnan(threshold):
+        raise _capi.NcaError("distance_transform: threshold = nan is not a number")
+    shape = tuple(vol.shape[-3:])
+    desc = _grid_desc(shape, bounds)
+    x = vol.detach().reshape((-1,) + shape).contiguous()
+    n_vol = x.shape[0]
+    out = torch.empty_like(x)
+    lib = _capi.lib()
+    nbytes = int(lib.nca_vol_edt_workspace(C.byref(desc), n_vol))
+    work = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _capi.check_edt(lib.nca_vol_edt(C.byref(desc), _capi.ptr(x), n_vol, threshold, 1 if inside else 0, _capi.ptr(out), _capi.ptr(work), nbytes,
+                                        _fused._stream()))
+    return out.reshape(vol.shape)
+
+
+def _directed(dist, mask, percentile):
+    """(count i64, sum f64, max f64, quantile f64) per leading index of ``dist`` over the nodes of ``mask``; NaN where the mask is empty."""
+    lead = mask.shape[:-3]
+    m = mask.reshape(-1, mask.shape[-3] * mask.shape[-2] * mask.shape[-1])
+    d = dist.reshape(m.shape).double()
+    n = m.sum(dim=1)
+    nan = torch.full((), math.nan, dtype=torch.float64, device=d.device)
+    total = torch.where(m, d, torch.zeros((), dtype=torch.float64, device=d.device)).sum(dim=1)
+    top = torch.where(m, d, torch.full((), -math.inf, dtype=torch.float64, device=d.device)).amax(dim=1)
+    quant = []
+    for k in range(m.shape[0]):          # the masked sets differ in size: one quantile per entry
+        quant.append(torch.quantile(d[k][m[k]], percentile / 100.0, interpolation="higher") if int(n[k]) else nan)
+    quant = torch.stack(quant) if quant else torch.empty(0, dtype=torch.float64, device=d.device)
+    empty = n == 0
+    return (n.reshape(lead), torch.where(empty, nan, total).reshape(lead), torch.where(empty, nan, top).reshape(lead), quant.reshape(lead))
+
+
+@torch.no_grad()
+def mask_distance_reductions(a: torch.Tensor, b: torch.Tensor, dist_to_a: torch.Tensor, dist_to_b: torch.Tensor, percentile: float = 95.0) -> dict:
+    """The reductions of ``mask_distances`` from the two masks ``a``, ``b`` (bool ``[..., n0, n1, n2]``) and the two distance maps (to the
+    nearest node of ``a`` / of ``b``, any float dtype): plain torch on whatever device the tensors live on."""
+    percentile = float(percentile)
+    if not 0.0 <= percentile <= 100.0:
+        raise _capi.NcaError(f"mask_distances: percentile = {percentile} is outside [0, 100]")
+    if not (a.shape == b.shape == dist_to_a.shape == dist_to_b.shape) or a.dim() < 3:
+        raise _capi.NcaError(f"mask_distances: masks {tuple(a.shape)}, {tuple(b.shape)} and maps {tuple(dist_to_a.shape)}, {tuple(dist_to_b.shape)} differ in shape")
+    n_a, sum_a, max_a, q_a = _directed(dist_to_b, a, percentile)
+    n_b, sum_b, max_b, q_b = _directed(dist_to_a, b, percentile)
+    either = (n_a == 0) | (n_b == 0)
+    nan = torch.full((), math.nan, dtype=torch.float64, device=sum_a.device)
+
+    def both(x):
+        return torch.where(either, nan, x)
+
+    return {"n_pred": n_a, "n_truth": n_b, "pred_to_truth": both(sum_a / n_a), "truth_to_pred": both(sum_b / n_b),
+            "assd": both((sum_a + sum_b) / (n_a + n_b)), "hausdorff": both(torch.maximum(max_a, max_b)), "hd_percentile": both(torch.maximum(q_a, q_b))}
+
+
+@torch.no_grad()
+def mask_distances(pred: torch.Tensor, truth: torch.Tensor, bounds, *, threshold: float, pred_threshold: Optional[float] = None,
+                   percentile: float = 95.0) -> dict:
+    """Distances between the masks ``A = pred > pred_threshold`` (``threshold`` when ``pred_threshold`` is ``None``) and
+    ``B = truth > threshold`` of two f32 stacks ``[..., n0, n1, n2]`` on the device, in the world units of ``bounds``: f64 device tensors of
+    the leading shape (a stack ``[P, n0, n1, n2]`` gives ``[P]``).
+
+    ``n_pred``, ``n_truth``: the node counts (i64).  ``pred_to_truth``: the mean over A of the distance to the nearest node of B;
+    ``truth_to_pred`` the other way round; ``assd``: the mean over both together, ``(sum_A + sum_B) / (|A| + |B|)``; ``hausdorff``: the
+    larger of the two directed maxima; ``hd_percentile``: the larger of the two directed ``percentile`` quantiles
+    (``torch.quantile(..., interpolation="higher")``).  The masks are whole bodies, not surfaces: a node of A inside B counts with distance 0.
+
+    Two ``distance_transform`` calls; the reductions are torch on the device.  An entry whose A or B is empty is NaN in every distance
+    (its counts are still returned); identical masks give exactly 0 in every distance."""
+    _check_volume(pred, "mask_distances", "pred")
+    _check_volume(truth, "mask_distances", "truth")
+    if pred.shape != truth.shape:
+        raise _capi.NcaError(f"mask_distances takes two stacks of one shape, got {tuple(pred.shape)} and {tuple(truth.shape)}")
+    if pred.device != truth.device:
+        raise _capi.NcaError(f"mask_distances: pred lives on {pred.device}, truth on {truth.device}")
+    threshold = float(threshold)
+    pred_threshold = threshold if pred_threshold is None else float(pred_threshold)
+    to_a = distance_transform(pred, bounds, threshold=pred_threshold)
+    to_b = distance_transform(truth, bounds, threshold=threshold)
+    return mask_distance_reductions(pred.detach() > pred_threshold, truth.detach() > threshold, to_a, to_b, percentile)
+
+
+def nearest_nodes(points, shape, bounds):
+    """(index i64 ``[n, 3]``, inside bool ``[n]``) of host points f64 ``[n, 3]``: the node nearest each point, ``floor(g_a + 0.5)`` with
+    ``g_a = (x_a - lo_a) inv_a`` of ``drr.grid_desc(shape, bounds)``; ``inside`` is False where an index falls outside the grid."""
+    desc = _grid_desc(shape, bounds)
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    lo, inv = np.array(list(desc.lo)), np.array(list(desc.inv))
+    idx = np.floor((pts - lo) * inv + 0.5)
+    n = np.array([int(s) for s in shape])
+    inside = np.isfinite(idx).all(axis=1) & (idx >= 0).all(axis=1) & (idx <= n - 1).all(axis=1)
+    return np.where(inside[:, None], idx, 0).astype(np.int64), inside
+
+
+@torch.no_grad()
+def coverage_reductions(dist: torch.Tensor, bounds, points, tol: float) -> dict:
+    """The reductions of ``centreline_coverage`` from the distance maps ``dist`` ``[P, n0, n1, n2]`` (or ``[n0, n1, n2]``): plain torch on
+    whatever device the maps live on."""
+    tol = float(tol)
+    if not tol >= 0.0:
+        raise _capi.NcaError(f"centreline_coverage: tol = {tol} is not a non-negative length")
+    if dist.dim() == 3:
+        dist = dist[None]
+    if isinstance(points, np.ndarray) and points.ndim == 2:
+        points = [points]
+    points = list(points)
+    if dist.dim() != 4 or len(points) not in (1, dist.shape[0]):
+        raise _capi.NcaError(f"centreline_coverage: {len(points)} point sets for maps of shape {tuple(dist.shape)}")
+    P, shape = dist.shape[0], tuple(dist.shape[1:])
+    cov, mean, n_pts, n_out = [], [], [], []
+    for p in range(P):
+        idx, inside = nearest_nodes(points[p if len(points) > 1 else 0], shape, bounds)
+        idx = torch.from_numpy(idx[inside]).to(dist.device)
+        d = dist[p][idx[:, 0], idx[:, 1], idx[:, 2]].double()
+        n_pts.append(int(inside.sum()))
+        n_out.append(int((~inside).sum()))
+        cov.append((d <= tol).double().mean() if n_pts[-1] else torch.full((), math.nan, dtype=torch.float64, device=dist.device))
+        mean.append(d.mean() if n_pts[-1] else torch.full((), math.nan, dtype=torch.float64, device=dist.device))
+    return {"coverage": torch.stack(cov), "mean_distance": torch.stack(mean), "n_points": torch.tensor(n_pts, dtype=torch.int64, device=dist.device),
+            "n_outside": torch.tensor(n_out, dtype=torch.int64, device=dist.device)}
+
+
+@torch.no_grad()
+def centreline_coverage(vol: torch.Tensor, bounds, points, *, threshold: float, tol: float) -> dict:
+    """How much of a known centreline a thresholded stack reaches.  ``vol`` is f32 ``[P, n0, n1, n2]`` (or one volume) on the device,
+    ``points`` a list of P host arrays f64 ``[n_p, 3]`` in world coordinates (``phantom.centreline_points``; one array serves every
+    phase).  Per phase, the distance map of ``vol > threshold`` is read at the node nearest each point, index ``floor(g_a + 0.5)``; a point
+    whose index falls outside the grid is dropped and counted in ``n_outside``.  Returns per phase: ``coverage`` (the share of the
+    remaining points with distance ``<= tol``, f64), ``mean_distance`` (f64; ``inf`` when the mask is empty), ``n_points`` and
+    ``n_outside`` (i64).  A phase with no point inside the grid is NaN.
+
+    The nearest-node read adds at most half a cell diagonal to a point's true distance from the mask (the node is at most that far from
+    the point), so a ``tol`` of one cell diagonal accepts centreline points up to one and a half diagonals away and never rejects one
+    within half a diagonal."""
+    _check_volume(vol, "centreline_coverage")
+    if vol.dim() not in (3, 4):
+        raise _capi.NcaError(f"centreline_coverage takes [P, n0, n1, n2] or [n0, n1, n2], got {tuple(vol.shape)}")
+    return coverage_reductions(distance_transform(vol, bounds, threshold=float(threshold)), bounds, points, tol)

@@ -240,6 +240,31 @@ def make_phantom(shape: Sequence[int], n_phases: int, geo: dict, *, seed: int = 
     return {"static": static, "dynamic": dynamic, "bounds": bounds, "ellipsoids": ell, "segments": seg}
 
 
+def centreline_points(segments, step: float) -> list:
+    """The centrelines of a segment table as points: a list of P host arrays f64 ``[n_p, 3]`` from ``segments`` f64 ``[P, N, 8]`` (a 2-D
+    table is one phase).  Each row (endpoints a, b) is sampled at ``a + t (b - a)``, ``t = k / m``, ``k = 0 .. m``,
+    ``m = max(1, ceil(|b - a| / step))``: consecutive points of a row are at most ``step`` apart, both endpoints are included (a joint of
+    two rows appears twice).  Host numpy, deterministic; what ``metrics.centreline_coverage`` takes."""
+    step = float(step)
+    if not (math.isfinite(step) and step > 0):
+        raise _capi.NcaError(f"centreline_points: step = {step} is not finite and positive")
+    seg = np.asarray(segments, dtype=np.float64)
+    if seg.ndim == 2:
+        seg = seg[None]
+    if seg.ndim != 3 or seg.shape[2] != 8 or not np.isfinite(seg[:, :, :6]).all():
+        raise _capi.NcaError(f"centreline_points: segments is a finite table [N,8] or [P,N,8], got {tuple(seg.shape)}")
+    out = []
+    for table in seg:
+        pts = []
+        for row in table:
+            a, b = row[0:3], row[3:6]
+            m = max(1, int(math.ceil(float(np.linalg.norm(b - a)) / step)))
+            t = np.arange(m + 1, dtype=np.float64) / m
+            pts.append(a[None, :] + t[:, None] * (b - a)[None, :])
+        out.append(np.concatenate(pts, axis=0) if pts else np.zeros((0, 3)))
+    return out
+
+
 @torch.no_grad()
 def volume_errors(pred: torch.Tensor, truth: torch.Tensor, threshold: Optional[float] = None) -> dict:
     """``{"rmse", "dice"}`` of a reconstructed volume (or stack) against the truth, in torch on the tensors' device: the root mean square

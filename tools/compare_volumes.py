@@ -1,0 +1,86 @@
+#!/usr/bin/env python3
+"""Compare two voxel reconstructions in 3-D: RMSE, the Dice coefficient and the distances of their thresholded masks.
+
+    python3 tools/compare_volumes.py fitted/ phantom/ --bounds -0.18,0.18,-0.18,0.18,-0.18,0.18 --threshold 3 [--pred-threshold 0.5] [--out x.json]
+
+Each directory holds static.npy [n0,n1,n2] and / or dynamic.npy [P,n0,n1,n2] as tools/make_phantom.py and tools/fit_volumes.py write them;
+the first is the prediction, the second the truth.  For every file both hold: phantom.volume_errors (RMSE over all nodes, Dice of the masks
+> threshold) and metrics.mask_distances (mean, Hausdorff and percentile distances between the masks, in the world units of --bounds, per
+volume of the stack).  --pred-threshold thresholds the prediction at a value of its own (a sparse-view fit rarely reaches the truth's
+densities); --pred-fraction F sets it to F times the prediction's own maximum instead.  Prints one JSON record, and writes it with --out.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import numpy as np  # noqa: E402
+
+from project_volumes import parse_bounds  # noqa: E402
+
+NAMES = ("static", "dynamic")
+
+
+def join_args(argv):
+    """--bounds usually starts with a minus sign, which argparse would take for an option: hand it over as --bounds=LIST."""
+    argv, out = list(argv), []
+    while argv:
+        a = argv.pop(0)
+        out.append(a + "=" + argv.pop(0) if a == "--bounds" and argv else a)
+    return out
+
+
+def parser():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("pred", help="directory of the reconstruction")
+    ap.add_argument("truth", help="directory of the truth")
+    ap.add_argument("--bounds", required=True, type=parse_bounds, help="x0,x1,y0,y1,z0,z1: positions of the first and last node per axis")
+    ap.add_argument("--threshold", required=True, type=float, help="a node belongs to the truth's mask when its value is above this")
+    ap.add_argument("--pred-threshold", type=float, default=None, help="threshold of the prediction (default: --threshold)")
+    ap.add_argument("--pred-fraction", type=float, default=None, help="threshold the prediction at this fraction of its own maximum")
+    ap.add_argument("--percentile", type=float, default=95.0)
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--out", default=None, help="also write the record to this file")
+    return ap
+
+
+def compare(pred, truth, bounds, threshold, pred_threshold, percentile):
+    """The record of one pair of device tensors of one shape."""
+    from nerfca_amd import metrics, phantom
+    rec = phantom.volume_errors(pred, truth, threshold)
+    rec["pred_threshold"] = threshold if pred_threshold is None else pred_threshold
+    dist = metrics.mask_distances(pred, truth, bounds, threshold=threshold, pred_threshold=pred_threshold, percentile=percentile)
+    rec.update({k: v.reshape(-1).tolist() for k, v in dist.items()})
+    return rec
+
+
+def main(argv=None):
+    args = parser().parse_args(join_args(sys.argv[1:] if argv is None else argv))
+    import torch
+    if args.pred_threshold is not None and args.pred_fraction is not None:
+        sys.exit("compare_volumes: --pred-threshold and --pred-fraction exclude each other")
+    out = {"pred": args.pred, "truth": args.truth, "bounds": [list(b) for b in args.bounds], "threshold": args.threshold, "percentile": args.percentile}
+    for name in NAMES:
+        a, b = (os.path.join(d, name + ".npy") for d in (args.pred, args.truth))
+        if not (os.path.exists(a) and os.path.exists(b)):
+            continue
+        pred, truth = (torch.from_numpy(np.load(p).astype(np.float32)).to(args.device) for p in (a, b))
+        if pred.shape != truth.shape:
+            sys.exit(f"compare_volumes: {a} is {tuple(pred.shape)}, {b} is {tuple(truth.shape)}")
+        pthr = args.pred_threshold if args.pred_fraction is None else args.pred_fraction * float(pred.max())
+        out[name] = compare(pred, truth, args.bounds, args.threshold, pthr, args.percentile)
+    if not any(n in out for n in NAMES):
+        sys.exit(f"compare_volumes: {args.pred} and {args.truth} share neither static.npy nor dynamic.npy")
+    text = json.dumps(out, indent=1)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
