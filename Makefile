@@ -17,6 +17,7 @@ all: $(OUT)
 $(CSRC)/nca_kernels_f32.o: $(CSRC)/nca_f32_layer.inc
 $(CSRC)/nca_kernels_wide.o $(CSRC)/nca_api.o: $(CSRC)/nca_wide.hpp
 $(CSRC)/nca_api.o: $(CSRC)/nca_api_wide.inc
+$(filter $(CSRC)/view/%,$(OBJS)): $(CSRC)/view/nca_view_common.hpp
 
 %.o: %.hip $(HDRS)
 	$(HIPCC) $(FLAGS) $(EXTRA) -c $< -o $@

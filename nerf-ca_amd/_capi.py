@@ -6,6 +6,7 @@ The library is the product's compute path.  There is no fallback: if it cannot b
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional
 
@@ -136,6 +137,23 @@ class NcaError(RuntimeError):
     pass
 
 
+def grid_desc(shape, bounds) -> NcaGrid:
+    """The NcaGrid of a volume of ``shape`` ``(n0, n1, n2)`` whose nodes are ``linspace(lo, hi, n)`` on each axis of ``bounds``:
+    ``lo`` and ``inv = (n - 1) / (hi - lo)``, in f64.  (Public as ``drr.grid_desc``.)"""
+    shape = tuple(int(n) for n in shape)
+    if len(shape) != 3 or len(bounds) != 3 or any(len(b) != 2 for b in bounds):
+        raise NcaError(f"a grid has three axes with (lo, hi) each: got shape {shape} and bounds {bounds!r}")
+    lo = [float(b[0]) for b in bounds]
+    hi = [float(b[1]) for b in bounds]
+    for a in range(3):
+        if shape[a] < 2:
+            raise NcaError(f"a grid has at least 2 nodes per axis: axis {a} has {shape[a]}")
+        if not (math.isfinite(lo[a]) and math.isfinite(hi[a]) and hi[a] > lo[a]):
+            raise NcaError(f"bounds of axis {a}: ({lo[a]}, {hi[a]}) is not a finite interval lo < hi")
+    inv = [(shape[a] - 1) / (hi[a] - lo[a]) for a in range(3)]
+    return NcaGrid(lo=(C.c_double * 3)(*lo), inv=(C.c_double * 3)(*inv), n=(C.c_int32 * 3)(*shape), reserved=0)
+
+
 _lib: Optional[C.CDLL] = None
 
 # name -> (restype, argtypes); every symbol include/nerfca_hip.h declares
@@ -245,46 +263,22 @@ def check(rc: int) -> int:
     return rc
 
 
-def check_view(rc: int) -> int:
-    """``check`` for the view-rendering entry points (nca_view_*, nca_image_normalize*): they keep their own message."""
-    if rc < 0:
-        raise NcaError(f"libnerfca_hip: {lib().nca_view_last_error().decode()} (code {rc})")
-    return rc
+def _section_check(last_error: str, what: str):
+    """``check`` for the entry points of a section that keeps its own message behind the symbol ``last_error``."""
+    def section_check(rc: int) -> int:
+        if rc < 0:
+            raise NcaError(f"libnerfca_hip: {getattr(lib(), last_error)().decode()} (code {rc})")
+        return rc
+    section_check.__doc__ = f"``check`` for the {what}: they keep their own message."
+    return section_check
 
 
-def check_drr(rc: int) -> int:
-    """``check`` for the volume-projection entry points (nca_drr_*): they keep their own message."""
-    if rc < 0:
-        raise NcaError(f"libnerfca_hip: {lib().nca_drr_last_error().decode()} (code {rc})")
-    return rc
-
-
-def check_vol(rc: int) -> int:
-    """``check`` for the volume-prior entry points (nca_vol_*): they keep their own message."""
-    if rc < 0:
-        raise NcaError(f"libnerfca_hip: {lib().nca_vol_last_error().decode()} (code {rc})")
-    return rc
-
-
-def check_phantom(rc: int) -> int:
-    """``check`` for the phantom entry points (nca_phantom_*): they keep their own message."""
-    if rc < 0:
-        raise NcaError(f"libnerfca_hip: {lib().nca_phantom_last_error().decode()} (code {rc})")
-    return rc
-
-
-def check_ssim(rc: int) -> int:
-    """``check`` for the image-similarity entry points (nca_ssim*): they keep their own message."""
-    if rc < 0:
-        raise NcaError(f"libnerfca_hip: {lib().nca_ssim_last_error().decode()} (code {rc})")
-    return rc
-
-
-def check_edt(rc: int) -> int:
-    """``check`` for the distance-transform entry points (nca_vol_edt*): they keep their own message."""
-    if rc < 0:
-        raise NcaError(f"libnerfca_hip: {lib().nca_edt_last_error().decode()} (code {rc})")
-    return rc
+check_view = _section_check("nca_view_last_error", "view-rendering entry points (nca_view_*, nca_image_normalize*)")
+check_drr = _section_check("nca_drr_last_error", "volume-projection entry points (nca_drr_*)")
+check_vol = _section_check("nca_vol_last_error", "volume-prior entry points (nca_vol_*)")
+check_phantom = _section_check("nca_phantom_last_error", "phantom entry points (nca_phantom_*)")
+check_ssim = _section_check("nca_ssim_last_error", "image-similarity entry points (nca_ssim*)")
+check_edt = _section_check("nca_edt_last_error", "distance-transform entry points (nca_vol_edt*)")
 
 
 def ptr(t) -> Optional[int]:

@@ -3,28 +3,16 @@
 // into training projections (drr.volume_teacher) and an exported 4-D density grid back into images (drr.project_sequence), and its
 // adjoint nca_drr_backproject, which scatters pixel gradients back onto the grid (the backward of drr.project_rays, what drr.fit_volumes
 // descends by).  This translation unit keeps its own thread-local error message (nca_drr_last_error): it shares no state with nca_api.hip or
-// nca_view.hip.
-#include <hip/hip_runtime.h>
+// the other sections.  The grid checks are nca_view_common.hpp's; both entry points share drr_check and the loop over groups of volumes.
+// The two kernels each place a sample on the grid in their own text, and the two texts must agree bit for bit: a shared routine was tried and
+// measured, and every form of it changed the adjoint's instructions ("Where the checks of csrc/view/ live").
 #include <atomic>
-#include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdint.h>
-#include "../../../include/nerfca_hip.h"
+#include <type_traits>
+#include "nca_view_common.hpp"
 
-static_assert(sizeof(NcaGrid) == 64, "NcaGrid is 64 bytes without padding");
+static thread_local NcaViewErr g_err;
 
-static thread_local char g_drr_err[256] = "";
-
-static int dfail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_drr_err, sizeof(g_drr_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-extern "C" const char* nca_drr_last_error(void) { return g_drr_err; }
+extern "C" const char* nca_drr_last_error(void) { return g_err.msg; }
 
 constexpr int DRR_BLOCK = 256;
 constexpr int DRR_MAX_GROUP = 8;          // volumes one launch keeps accumulators for
@@ -33,7 +21,7 @@ constexpr int DRR_DEFAULT_SPLIT = 4;      // the structure tools/drr_bench.py me
 static std::atomic<int> g_drr_split{DRR_DEFAULT_SPLIT};
 
 extern "C" int nca_drr_set_split(int32_t split) {
-    if (split != 1 && split != 4) return dfail(NCA_E_INVALID, "nca_drr_set_split: split = %d is neither 1 nor 4", (int)split);
+    if (split != 1 && split != 4) return g_err.fail(NCA_E_INVALID, "nca_drr_set_split: split = %d is neither 1 nor 4", (int)split);
     g_drr_split.store(split);
     return NCA_OK;
 }
@@ -131,62 +119,60 @@ __global__ void __launch_bounds__(DRR_BLOCK) drr_kernel(NcaGrid g, const float* 
     }
 }
 
-template <int NV>
-static void launch_group(int split, dim3 grid, hipStream_t st, const NcaGrid& g, const float* vol, int64_t voxels, int64_t R, int32_t S, const double* origins,
-                         const double* dirs, const float* z, const double* dists, double i0, double* pix) {
-    if (split == 4)
-        hipLaunchKernelGGL((drr_kernel<NV, 4>), grid, dim3(DRR_BLOCK), 0, st, g, vol, voxels, R, S, origins, dirs, z, dists, i0, pix);
-    else
-        hipLaunchKernelGGL((drr_kernel<NV, 1>), grid, dim3(DRR_BLOCK), 0, st, g, vol, voxels, R, S, origins, dirs, z, dists, i0, pix);
+// The checks both entry points make after their pointers: the counts, the grid with `node_bytes` bytes per node of a volume, and the f64 per
+// ray and volume.  On success *g and *voxels are set.
+static int drr_check(const char* who, const NcaGrid* grid, int32_t n_vol, int64_t R, int32_t S, int node_bytes, NcaGrid* g, int64_t* voxels) {
+    if (n_vol <= 0) return g_err.fail(NCA_E_INVALID, "%s: n_vol = %d is not positive", who, (int)n_vol);
+    if (R <= 0) return g_err.fail(NCA_E_INVALID, "%s: R = %lld is not positive", who, (long long)R);
+    if (S <= 0) return g_err.fail(NCA_E_INVALID, "%s: S = %d is not positive", who, (int)S);
+    const int rc = nca_check_grid(g_err, who, grid, n_vol, node_bytes, "volumes", g, voxels);
+    if (rc != NCA_OK) return rc;
+    if (R > INT64_MAX / 8 / n_vol) return g_err.fail(NCA_E_INVALID, "%s: R = %lld rays x %d volumes overflows int64", who, (long long)R, (int)n_vol);
+    return NCA_OK;
+}
+
+// launch(NV, v0) for groups of NV = 8, 4, 2, 1 volumes that start at volume v0: the kernels keep NV sets of accumulators in registers, and a
+// volume's result is the same whatever group it is in.  NV arrives as a std::integral_constant.
+template <typename Launch>
+static void drr_for_groups(int32_t n_vol, Launch launch) {
+    for (int32_t v0 = 0; v0 < n_vol;) {
+        const int32_t left = n_vol - v0;
+        if (left >= DRR_MAX_GROUP) launch(std::integral_constant<int, DRR_MAX_GROUP>{}, v0), v0 += DRR_MAX_GROUP;
+        else if (left >= 4) launch(std::integral_constant<int, 4>{}, v0), v0 += 4;
+        else if (left >= 2) launch(std::integral_constant<int, 2>{}, v0), v0 += 2;
+        else launch(std::integral_constant<int, 1>{}, v0), v0 += 1;
+    }
 }
 
 extern "C" int nca_drr_project(const NcaGrid* grid, const float* vol, int32_t n_vol, int64_t R, int32_t S, const double* origins, const double* dirs,
                                const float* z, const double* dists, double i0, double* pix, void* stream) {
-    if (!grid) return dfail(NCA_E_INVALID, "nca_drr_project: the grid descriptor is NULL");
-    if (!vol) return dfail(NCA_E_INVALID, "nca_drr_project: vol is NULL");
-    if (!origins) return dfail(NCA_E_INVALID, "nca_drr_project: origins is NULL");
-    if (!dirs) return dfail(NCA_E_INVALID, "nca_drr_project: dirs is NULL");
-    if (!z) return dfail(NCA_E_INVALID, "nca_drr_project: z is NULL");
-    if (!dists) return dfail(NCA_E_INVALID, "nca_drr_project: dists is NULL");
-    if (!pix) return dfail(NCA_E_INVALID, "nca_drr_project: pix is NULL");
-    if (n_vol <= 0) return dfail(NCA_E_INVALID, "nca_drr_project: n_vol = %d is not positive", (int)n_vol);
-    if (R <= 0) return dfail(NCA_E_INVALID, "nca_drr_project: R = %lld is not positive", (long long)R);
-    if (S <= 0) return dfail(NCA_E_INVALID, "nca_drr_project: S = %d is not positive", (int)S);
-    const NcaGrid g = *grid;
-    if (g.reserved != 0) return dfail(NCA_E_INVALID, "nca_drr_project: reserved = %d is not 0", (int)g.reserved);
-    for (int a = 0; a < 3; ++a) {
-        if (g.n[a] < 2) return dfail(NCA_E_INVALID, "nca_drr_project: n[%d] = %d is less than 2 nodes", a, (int)g.n[a]);
-        if (!isfinite(g.lo[a])) return dfail(NCA_E_INVALID, "nca_drr_project: lo[%d] = %g is not finite", a, g.lo[a]);
-        if (!isfinite(g.inv[a])) return dfail(NCA_E_INVALID, "nca_drr_project: inv[%d] = %g is not finite", a, g.inv[a]);
-        if (!(g.inv[a] > 0.0)) return dfail(NCA_E_INVALID, "nca_drr_project: inv[%d] = %g is not positive", a, g.inv[a]);
-    }
-    // n0 n1 < 2^62 always; the bytes of all volumes must fit int64
-    const int64_t n01 = (int64_t)g.n[0] * g.n[1];
-    if (n01 > (INT64_MAX / 4 / n_vol) / g.n[2])
-        return dfail(NCA_E_INVALID, "nca_drr_project: %d volumes of %d x %d x %d voxels overflow int64", (int)n_vol, (int)g.n[0], (int)g.n[1], (int)g.n[2]);
-    const int64_t voxels = n01 * g.n[2];
-    if (R > INT64_MAX / 8 / n_vol) return dfail(NCA_E_INVALID, "nca_drr_project: R = %lld rays x %d volumes overflows int64", (long long)R, (int)n_vol);
+    const char* who = "nca_drr_project";
+    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    NCA_REFUSE_NULL(g_err, who, vol);
+    NCA_REFUSE_NULL(g_err, who, origins);
+    NCA_REFUSE_NULL(g_err, who, dirs);
+    NCA_REFUSE_NULL(g_err, who, z);
+    NCA_REFUSE_NULL(g_err, who, dists);
+    NCA_REFUSE_NULL(g_err, who, pix);
+    NcaGrid g;
+    int64_t voxels;
+    const int rc = drr_check(who, grid, n_vol, R, S, 4, &g, &voxels);
+    if (rc != NCA_OK) return rc;
     const int split = g_drr_split.load();
     const int64_t rays_per_block = DRR_BLOCK / split, blocks = (R + rays_per_block - 1) / rays_per_block;
-    if (blocks > 0x7fffffffLL) return dfail(NCA_E_INVALID, "nca_drr_project: R = %lld is more than one launch covers", (long long)R);
+    if (blocks > 0x7fffffffLL) return g_err.fail(NCA_E_INVALID, "%s: R = %lld is more than one launch covers", who, (long long)R);
     const dim3 grd((unsigned)blocks);
     const hipStream_t st = (hipStream_t)stream;
-    for (int32_t v0 = 0; v0 < n_vol;) {          // groups of 8, 4, 2, 1 volumes: each volume's sum is the same whatever group it is in
-        const int32_t left = n_vol - v0;
-        const int32_t nv = left >= DRR_MAX_GROUP ? DRR_MAX_GROUP : (left >= 4 ? 4 : (left >= 2 ? 2 : 1));
+    drr_for_groups(n_vol, [&](auto nv, int32_t v0) {
+        constexpr int NV = decltype(nv)::value;
         const float* vp = vol + (int64_t)v0 * voxels;
         double* pp = pix + (int64_t)v0 * R;
-        switch (nv) {
-            case 8: launch_group<8>(split, grd, st, g, vp, voxels, R, S, origins, dirs, z, dists, i0, pp); break;
-            case 4: launch_group<4>(split, grd, st, g, vp, voxels, R, S, origins, dirs, z, dists, i0, pp); break;
-            case 2: launch_group<2>(split, grd, st, g, vp, voxels, R, S, origins, dirs, z, dists, i0, pp); break;
-            default: launch_group<1>(split, grd, st, g, vp, voxels, R, S, origins, dirs, z, dists, i0, pp); break;
-        }
-        v0 += nv;
-    }
-    const hipError_t e = hipGetLastError();          // once, after the last group
-    if (e != hipSuccess) return dfail(NCA_E_HIP, "nca_drr_project: %s", hipGetErrorString(e));
-    return NCA_OK;
+        if (split == 4)
+            hipLaunchKernelGGL((drr_kernel<NV, 4>), grd, dim3(DRR_BLOCK), 0, st, g, vp, voxels, R, S, origins, dirs, z, dists, i0, pp);
+        else
+            hipLaunchKernelGGL((drr_kernel<NV, 1>), grd, dim3(DRR_BLOCK), 0, st, g, vp, voxels, R, S, origins, dirs, z, dists, i0, pp);
+    });
+    return nca_launched(g_err, who);          // once, after the last group
 }
 
 // ---- back-projection: the adjoint of nca_drr_project in the volumes ---------------------------------------------------------------------
@@ -196,7 +182,7 @@ constexpr int DRR_DEFAULT_BACK_RUNS = 1;   // the structure tools/drr_grad_bench
 static std::atomic<int> g_drr_back_runs{DRR_DEFAULT_BACK_RUNS};
 
 extern "C" int nca_drr_set_backproject_runs(int32_t runs) {
-    if (runs != 0 && runs != 1) return dfail(NCA_E_INVALID, "nca_drr_set_backproject_runs: runs = %d is neither 0 nor 1", (int)runs);
+    if (runs != 0 && runs != 1) return g_err.fail(NCA_E_INVALID, "nca_drr_set_backproject_runs: runs = %d is neither 0 nor 1", (int)runs);
     g_drr_back_runs.store(runs);
     return NCA_OK;
 }
@@ -309,61 +295,34 @@ __global__ void __launch_bounds__(DRR_BLOCK) drr_back_kernel(NcaGrid g, int64_t 
     }
 }
 
-template <int NV>
-static void launch_back_group(bool runs, dim3 grid, hipStream_t st, const NcaGrid& g, int64_t voxels, int64_t R, int32_t S, const double* origins, const double* dirs,
-                              const float* z, const double* dists, const double* g_pix, double* g_vol) {
-    if (runs)
-        hipLaunchKernelGGL((drr_back_kernel<NV, true>), grid, dim3(DRR_BLOCK), 0, st, g, voxels, R, S, origins, dirs, z, dists, g_pix, g_vol);
-    else
-        hipLaunchKernelGGL((drr_back_kernel<NV, false>), grid, dim3(DRR_BLOCK), 0, st, g, voxels, R, S, origins, dirs, z, dists, g_pix, g_vol);
-}
-
 extern "C" int nca_drr_backproject(const NcaGrid* grid, int32_t n_vol, int64_t R, int32_t S, const double* origins, const double* dirs, const float* z,
                                    const double* dists, const double* g_pix, double* g_vol, void* stream) {
-    if (!grid) return dfail(NCA_E_INVALID, "nca_drr_backproject: the grid descriptor is NULL");
-    if (!origins) return dfail(NCA_E_INVALID, "nca_drr_backproject: origins is NULL");
-    if (!dirs) return dfail(NCA_E_INVALID, "nca_drr_backproject: dirs is NULL");
-    if (!z) return dfail(NCA_E_INVALID, "nca_drr_backproject: z is NULL");
-    if (!dists) return dfail(NCA_E_INVALID, "nca_drr_backproject: dists is NULL");
-    if (!g_pix) return dfail(NCA_E_INVALID, "nca_drr_backproject: g_pix is NULL");
-    if (!g_vol) return dfail(NCA_E_INVALID, "nca_drr_backproject: g_vol is NULL");
-    if (n_vol <= 0) return dfail(NCA_E_INVALID, "nca_drr_backproject: n_vol = %d is not positive", (int)n_vol);
-    if (R <= 0) return dfail(NCA_E_INVALID, "nca_drr_backproject: R = %lld is not positive", (long long)R);
-    if (S <= 0) return dfail(NCA_E_INVALID, "nca_drr_backproject: S = %d is not positive", (int)S);
-    if (S > INT32_MAX - DRR_BACK_PARTS) return dfail(NCA_E_INVALID, "nca_drr_backproject: S = %d is more than one launch covers", (int)S);
-    const NcaGrid g = *grid;
-    if (g.reserved != 0) return dfail(NCA_E_INVALID, "nca_drr_backproject: reserved = %d is not 0", (int)g.reserved);
-    for (int a = 0; a < 3; ++a) {
-        if (g.n[a] < 2) return dfail(NCA_E_INVALID, "nca_drr_backproject: n[%d] = %d is less than 2 nodes", a, (int)g.n[a]);
-        if (!isfinite(g.lo[a])) return dfail(NCA_E_INVALID, "nca_drr_backproject: lo[%d] = %g is not finite", a, g.lo[a]);
-        if (!isfinite(g.inv[a])) return dfail(NCA_E_INVALID, "nca_drr_backproject: inv[%d] = %g is not finite", a, g.inv[a]);
-        if (!(g.inv[a] > 0.0)) return dfail(NCA_E_INVALID, "nca_drr_backproject: inv[%d] = %g is not positive", a, g.inv[a]);
-    }
-    // the bytes of all f64 gradient volumes must fit int64
-    const int64_t n01 = (int64_t)g.n[0] * g.n[1];
-    if (n01 > (INT64_MAX / 8 / n_vol) / g.n[2])
-        return dfail(NCA_E_INVALID, "nca_drr_backproject: %d volumes of %d x %d x %d voxels overflow int64", (int)n_vol, (int)g.n[0], (int)g.n[1], (int)g.n[2]);
-    const int64_t voxels = n01 * g.n[2];
-    if (R > INT64_MAX / 8 / n_vol) return dfail(NCA_E_INVALID, "nca_drr_backproject: R = %lld rays x %d volumes overflows int64", (long long)R, (int)n_vol);
+    const char* who = "nca_drr_backproject";
+    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    NCA_REFUSE_NULL(g_err, who, origins);
+    NCA_REFUSE_NULL(g_err, who, dirs);
+    NCA_REFUSE_NULL(g_err, who, z);
+    NCA_REFUSE_NULL(g_err, who, dists);
+    NCA_REFUSE_NULL(g_err, who, g_pix);
+    NCA_REFUSE_NULL(g_err, who, g_vol);
+    NcaGrid g;
+    int64_t voxels;
+    const int rc = drr_check(who, grid, n_vol, R, S, 8, &g, &voxels);          // the gradient volumes are f64
+    if (rc != NCA_OK) return rc;
+    if (S > INT32_MAX - DRR_BACK_PARTS) return g_err.fail(NCA_E_INVALID, "%s: S = %d is more than one launch covers", who, (int)S);
     const bool runs = g_drr_back_runs.load() != 0;
     const int64_t rays_per_block = DRR_BLOCK / DRR_BACK_PARTS, blocks = (R + rays_per_block - 1) / rays_per_block;
-    if (blocks > 0x7fffffffLL) return dfail(NCA_E_INVALID, "nca_drr_backproject: R = %lld is more than one launch covers", (long long)R);
+    if (blocks > 0x7fffffffLL) return g_err.fail(NCA_E_INVALID, "%s: R = %lld is more than one launch covers", who, (long long)R);
     const dim3 grd((unsigned)blocks);
     const hipStream_t st = (hipStream_t)stream;
-    for (int32_t v0 = 0; v0 < n_vol;) {          // groups of 8, 4, 2, 1 volumes, as in nca_drr_project
-        const int32_t left = n_vol - v0;
-        const int32_t nv = left >= DRR_MAX_GROUP ? DRR_MAX_GROUP : (left >= 4 ? 4 : (left >= 2 ? 2 : 1));
+    drr_for_groups(n_vol, [&](auto nv, int32_t v0) {
+        constexpr int NV = decltype(nv)::value;
         const double* gp = g_pix + (int64_t)v0 * R;
         double* gv = g_vol + (int64_t)v0 * voxels;
-        switch (nv) {
-            case 8: launch_back_group<8>(runs, grd, st, g, voxels, R, S, origins, dirs, z, dists, gp, gv); break;
-            case 4: launch_back_group<4>(runs, grd, st, g, voxels, R, S, origins, dirs, z, dists, gp, gv); break;
-            case 2: launch_back_group<2>(runs, grd, st, g, voxels, R, S, origins, dirs, z, dists, gp, gv); break;
-            default: launch_back_group<1>(runs, grd, st, g, voxels, R, S, origins, dirs, z, dists, gp, gv); break;
-        }
-        v0 += nv;
-    }
-    const hipError_t e = hipGetLastError();          // once, after the last group
-    if (e != hipSuccess) return dfail(NCA_E_HIP, "nca_drr_backproject: %s", hipGetErrorString(e));
-    return NCA_OK;
+        if (runs)
+            hipLaunchKernelGGL((drr_back_kernel<NV, true>), grd, dim3(DRR_BLOCK), 0, st, g, voxels, R, S, origins, dirs, z, dists, gp, gv);
+        else
+            hipLaunchKernelGGL((drr_back_kernel<NV, false>), grd, dim3(DRR_BLOCK), 0, st, g, voxels, R, S, origins, dirs, z, dists, gp, gv);
+    });
+    return nca_launched(g_err, who);          // once, after the last group
 }

@@ -2,25 +2,13 @@
 // and the vessel distances built on it.  Separable, three launches: the integer distance g to the nearest feature of a row (one wave per
 // row, features as ballot masks), then the lower envelope min_j (w d^2 + f(j)) along axis 1 and along axis 0 by a pruned outward search over
 // a line staged in LDS.  Every node of every stage is written once by one thread: no atomics, the same bits on every run.  This translation
-// unit keeps its own thread-local error message (nca_edt_last_error): it shares no state with the other sections.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdint.h>
-#include "../../../include/nerfca_hip.h"
+// unit keeps its own thread-local error message (nca_edt_last_error): it shares no state with the other sections.  The grid checks and the
+// workspace refusal are nca_view_common.hpp's; the limit on an axis is checked here, after them.
+#include "nca_view_common.hpp"
 
-static thread_local char g_edt_err[256] = "";
+static thread_local NcaViewErr g_err;
 
-static int efail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_edt_err, sizeof(g_edt_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-extern "C" const char* nca_edt_last_error(void) { return g_edt_err; }
+extern "C" const char* nca_edt_last_error(void) { return g_err.msg; }
 
 constexpr int ED_BLOCK = 256, ED_WAVES = ED_BLOCK / 64;
 constexpr int ED_CHUNKS = NCA_EDT_MAX_AXIS / 64;          // ballot masks of the longest row
@@ -147,24 +135,17 @@ __global__ void __launch_bounds__(ED_BLOCK) edt_line_kernel(int32_t len, int64_t
 
 // The checks the query and the entry point share; on success *nodes is n_vol n0 n1 n2.
 static int edt_check(const char* who, const NcaGrid* grid, int32_t n_vol, int64_t* nodes) {
-    if (!grid) return efail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
-    if (n_vol <= 0) return efail(NCA_E_INVALID, "%s: n_vol = %d is not positive", who, (int)n_vol);
-    const NcaGrid g = *grid;
-    if (g.reserved != 0) return efail(NCA_E_INVALID, "%s: reserved = %d is not 0", who, (int)g.reserved);
-    for (int a = 0; a < 3; ++a) {
-        if (g.n[a] < 2) return efail(NCA_E_INVALID, "%s: n[%d] = %d is less than 2 nodes", who, a, (int)g.n[a]);
-        if (!isfinite(g.lo[a])) return efail(NCA_E_INVALID, "%s: lo[%d] = %g is not finite", who, a, g.lo[a]);
-        if (!isfinite(g.inv[a])) return efail(NCA_E_INVALID, "%s: inv[%d] = %g is not finite", who, a, g.inv[a]);
-        if (!(g.inv[a] > 0.0)) return efail(NCA_E_INVALID, "%s: inv[%d] = %g is not positive", who, a, g.inv[a]);
-    }
-    // n0 n1 < 2^62 always; the 12 bytes per node of the workspace (and the 4 of the volumes) must fit int64
-    const int64_t n01 = (int64_t)g.n[0] * g.n[1];
-    if (n01 > (INT64_MAX / 16 / n_vol) / g.n[2])
-        return efail(NCA_E_INVALID, "%s: %d volumes of %d x %d x %d voxels overflow int64", who, (int)n_vol, (int)g.n[0], (int)g.n[1], (int)g.n[2]);
+    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    if (n_vol <= 0) return g_err.fail(NCA_E_INVALID, "%s: n_vol = %d is not positive", who, (int)n_vol);
+    // the 12 bytes per node of the workspace (and the 4 of the volumes) must fit int64
+    NcaGrid g;
+    int64_t voxels;
+    const int rc = nca_check_grid(g_err, who, grid, n_vol, 16, "volumes", &g, &voxels);
+    if (rc != NCA_OK) return rc;
     for (int a = 0; a < 3; ++a)
         if (g.n[a] > NCA_EDT_MAX_AXIS)
-            return efail(NCA_E_UNSUPPORTED, "%s: n[%d] = %d is longer than NCA_EDT_MAX_AXIS = %d", who, a, (int)g.n[a], (int)NCA_EDT_MAX_AXIS);
-    *nodes = n01 * g.n[2] * n_vol;
+            return g_err.fail(NCA_E_UNSUPPORTED, "%s: n[%d] = %d is longer than NCA_EDT_MAX_AXIS = %d", who, a, (int)g.n[a], (int)NCA_EDT_MAX_AXIS);
+    *nodes = voxels * n_vol;
     return NCA_OK;
 }
 
@@ -177,11 +158,11 @@ extern "C" size_t nca_vol_edt_workspace(const NcaGrid* grid, int32_t n_vol) {
 extern "C" int nca_vol_edt(const NcaGrid* grid, const float* vol, int32_t n_vol, double threshold, int32_t invert, float* out, void* work, size_t work_bytes,
                            void* stream) {
     const char* who = "nca_vol_edt";
-    if (!grid) return efail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
-    if (!vol) return efail(NCA_E_INVALID, "%s: vol is NULL", who);
-    if (!out) return efail(NCA_E_INVALID, "%s: out is NULL", who);
-    if (invert != 0 && invert != 1) return efail(NCA_E_INVALID, "%s: invert = %d is neither 0 nor 1", who, (int)invert);
-    if (threshold != threshold) return efail(NCA_E_INVALID, "%s: threshold = %g is not a number", who, threshold);
+    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    NCA_REFUSE_NULL(g_err, who, vol);
+    NCA_REFUSE_NULL(g_err, who, out);
+    if (invert != 0 && invert != 1) return g_err.fail(NCA_E_INVALID, "%s: invert = %d is neither 0 nor 1", who, (int)invert);
+    if (threshold != threshold) return g_err.fail(NCA_E_INVALID, "%s: threshold = %g is not a number", who, threshold);
     int64_t nodes;
     const int rc = edt_check(who, grid, n_vol, &nodes);
     if (rc != NCA_OK) return rc;
@@ -193,12 +174,10 @@ extern "C" int nca_vol_edt(const NcaGrid* grid, const float* vol, int32_t n_vol,
     const int64_t tiles_0 = (plane + ED_TC - 1) / ED_TC, blocks_0 = (int64_t)n_vol * tiles_0;
     const int64_t most = blocks_r > blocks_1 ? (blocks_r > blocks_0 ? blocks_r : blocks_0) : (blocks_1 > blocks_0 ? blocks_1 : blocks_0);
     if (most > ED_MAX_BLOCKS)
-        return efail(NCA_E_INVALID, "%s: %d volumes of %d x %d x %d voxels make %lld tiles, more than one launch covers", who, (int)n_vol, (int)n0, (int)n1, (int)n2,
+        return g_err.fail(NCA_E_INVALID, "%s: %d volumes of %d x %d x %d voxels make %lld tiles, more than one launch covers", who, (int)n_vol, (int)n0, (int)n1, (int)n2,
                      (long long)most);
-    const size_t need = nca_vol_edt_workspace(grid, n_vol);
-    if (!work || work_bytes < need)
-        return efail(NCA_E_WORKSPACE, "%s: the workspace holds %llu bytes%s, %llu are needed", who, (unsigned long long)work_bytes, work ? "" : " (work is NULL)",
-                     (unsigned long long)need);
+    const int rcw = nca_check_workspace(g_err, who, work, work_bytes, nca_vol_edt_workspace(grid, n_vol));
+    if (rcw != NCA_OK) return rcw;
     double w[3];
     for (int a = 0; a < 3; ++a) {
         const double h = 1.0 / g.inv[a];
@@ -212,7 +191,5 @@ extern "C" int nca_vol_edt(const NcaGrid* grid, const float* vol, int32_t n_vol,
                        (const void*)gd, (void*)b);
     hipLaunchKernelGGL((edt_line_kernel<false>), dim3((unsigned)blocks_0), dim3(ED_BLOCK), (size_t)n0 * ED_TC * sizeof(double), s, n0, plane, tiles_0, w[0], 0.0,
                        (const void*)b, (void*)out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return efail(NCA_E_HIP, "%s: %s", who, hipGetErrorString(e));
-    return NCA_OK;
+    return nca_launched(g_err, who);
 }

@@ -1,36 +1,21 @@
 // nca_phantom.hip -- rasterises a procedural 4-D phantom (include/nerfca_hip.h, "phantom"): per heart phase a table of soft ellipsoids (the
 // static thorax, additive) and a table of tapered capsules (the vessels, a maximum) into the f32 grids drr / export / synthetic take.  One
 // pass: every node of every phase is written once by one thread, no atomics, the same bits on every run.  This translation unit keeps its
-// own thread-local error message (nca_phantom_last_error): it shares no state with the other sections.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdint.h>
+// own thread-local error message (nca_phantom_last_error): it shares no state with the other sections.  The grid checks, the tile count
+// and the tile's indexing are nca_view_common.hpp's.
 #include <atomic>
-#include "../../../include/nerfca_hip.h"
+#include "nca_view_common.hpp"
 
-static thread_local char g_ph_err[256] = "";
+static thread_local NcaViewErr g_err;
 static std::atomic<int> g_ph_cull{1};          // the faster of the two as measured by tools/phantom_bench.py
 
-static int pfail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_ph_err, sizeof(g_ph_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+extern "C" const char* nca_phantom_last_error(void) { return g_err.msg; }
 
-extern "C" const char* nca_phantom_last_error(void) { return g_ph_err; }
-
-// A workgroup owns a tile of 4 x 8 x 64 nodes of one phase.  Wave w of the eight takes the rows (j0, j1) = (k, w), k = 0 .. 3, with its 64
-// lanes along the last (contiguous) axis: 4 nodes per thread, every store a full line.
-constexpr int PH_T0 = 4, PH_T1 = 8, PH_T2 = 64;
-constexpr int PH_BLOCK = 512, PH_WAVES = PH_BLOCK / 64;
-constexpr int PH_NPT = PH_T0 * PH_T1 * PH_T2 / PH_BLOCK;
+// A workgroup owns a tile of 4 x 8 x 64 nodes (nca_view_common.hpp) of one phase.
+constexpr int PH_T0 = NCA_TILE0, PH_T1 = NCA_TILE1, PH_T2 = NCA_TILE2;
+constexpr int PH_BLOCK = NCA_TILE_BLOCK, PH_WAVES = NCA_TILE_WAVES, PH_NPT = NCA_TILE_NPT;
 constexpr int PH_BATCH = NCA_PHANTOM_SEG_BATCH;
 constexpr int PH_REC = 9;          // a staged segment: a[3], e[3], ee, ra, rb - ra
-static_assert(PH_T2 == 64 && PH_WAVES == PH_T1 && PH_NPT == PH_T0, "a wave is one row of the tile: node k of a thread is (k, wave, lane)");
 static_assert(PH_BATCH == PH_BLOCK, "staging: thread t of the block tests segment t of the batch");
 
 __device__ __forceinline__ double ph_clamp01(double v) { return fmin(fmax(v, 0.0), 1.0); }
@@ -48,15 +33,15 @@ __global__ void __launch_bounds__(PH_BLOCK) phantom_kernel(NcaGrid g, int64_t vo
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int32_t n0 = g.n[0], n1 = g.n[1], n2 = g.n[2];
     const int64_t bid = blockIdx.x;
-    const int64_t phase = bid / tiles, tile = bid % tiles;
-    const int32_t base2 = (int32_t)(tile % nb2) * PH_T2, base1 = (int32_t)((tile / nb2) % nb1) * PH_T1, base0 = (int32_t)(tile / ((int64_t)nb2 * nb1)) * PH_T0;
+    const int64_t phase = bid / tiles;
+    const NcaTile tile = nca_tile(bid % tiles, nb1, nb2);
+    const int32_t base0 = tile.base0, base1 = tile.base1, base2 = tile.base2;
     const double h0 = __ddiv_rn(1.0, g.inv[0]), h1 = __ddiv_rn(1.0, g.inv[1]), h2 = __ddiv_rn(1.0, g.inv[2]);
     auto pos = [](double lo, int32_t i, double h) -> double { return __dadd_rn(lo, __dmul_rn((double)i, h)); };
 
     // the thread's own nodes: (j0, j1, j2) = (k, wave, lane)
-    const int32_t i1 = base1 + wave, i2 = base2 + lane;
-    const bool ok12 = i2 < n2 && i1 < n1;
-    const int64_t off_t = ((int64_t)base0 * n1 + i1) * n2 + i2;
+    const NcaTileNodes nodes = nca_tile_nodes(tile, wave, lane, n0, n1, n2);
+    const int32_t i1 = nodes.i1, i2 = nodes.i2;
     const double x1 = pos(g.lo[1], i1, h1), x2 = pos(g.lo[2], i2, h2);
     double x0[PH_NPT], best[PH_NPT];
 #pragma unroll
@@ -151,12 +136,12 @@ __global__ void __launch_bounds__(PH_BLOCK) phantom_kernel(NcaGrid g, int64_t vo
     float* outp = out + phase * voxels;
 #pragma unroll
     for (int k = 0; k < PH_NPT; ++k) {
-        if (ok12 && base0 + k < n0) outp[off_t + (int64_t)k * n1 * n2] = (float)__dadd_rn(bg[k], __dmul_rn(rho_v, best[k]));
+        if (nodes.live(k)) outp[nodes.off(k)] = (float)__dadd_rn(bg[k], __dmul_rn(rho_v, best[k]));
     }
 }
 
 extern "C" int nca_phantom_set_cull(int32_t on) {
-    if (on != 0 && on != 1) return pfail(NCA_E_INVALID, "nca_phantom_set_cull: on = %d is neither 0 nor 1", (int)on);
+    if (on != 0 && on != 1) return g_err.fail(NCA_E_INVALID, "nca_phantom_set_cull: on = %d is neither 0 nor 1", (int)on);
     g_ph_cull.store(on);
     return NCA_OK;
 }
@@ -166,42 +151,26 @@ extern "C" int nca_phantom_get_cull(void) { return g_ph_cull.load(); }
 extern "C" int nca_phantom_voxelize(const NcaGrid* grid, int32_t n_phase, int32_t n_ell, const double* ell, int32_t n_seg, const double* seg, double rho_v,
                                     double edge, float* out, void* stream) {
     const char* who = "nca_phantom_voxelize";
-    if (!grid) return pfail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
-    if (!out) return pfail(NCA_E_INVALID, "%s: out is NULL", who);
-    if (n_phase <= 0) return pfail(NCA_E_INVALID, "%s: n_phase = %d is not positive", who, (int)n_phase);
-    if (n_ell < 0) return pfail(NCA_E_INVALID, "%s: n_ell = %d is negative", who, (int)n_ell);
-    if (n_seg < 0) return pfail(NCA_E_INVALID, "%s: n_seg = %d is negative", who, (int)n_seg);
-    if (n_ell == 0 && n_seg == 0) return pfail(NCA_E_INVALID, "%s: n_ell = 0 and n_seg = 0: there is nothing to rasterise", who);
-    if (n_ell > 0 && !ell) return pfail(NCA_E_INVALID, "%s: ell is NULL with n_ell = %d", who, (int)n_ell);
-    if (n_seg > 0 && !seg) return pfail(NCA_E_INVALID, "%s: seg is NULL with n_seg = %d", who, (int)n_seg);
-    if (!(isfinite(edge) && edge > 0.0)) return pfail(NCA_E_INVALID, "%s: edge = %g is not finite and positive", who, edge);
-    if (!isfinite(rho_v)) return pfail(NCA_E_INVALID, "%s: rho_v = %g is not finite", who, rho_v);
-    const NcaGrid g = *grid;
-    if (g.reserved != 0) return pfail(NCA_E_INVALID, "%s: reserved = %d is not 0", who, (int)g.reserved);
-    for (int a = 0; a < 3; ++a) {
-        if (g.n[a] < 2) return pfail(NCA_E_INVALID, "%s: n[%d] = %d is less than 2 nodes", who, a, (int)g.n[a]);
-        if (!isfinite(g.lo[a])) return pfail(NCA_E_INVALID, "%s: lo[%d] = %g is not finite", who, a, g.lo[a]);
-        if (!isfinite(g.inv[a])) return pfail(NCA_E_INVALID, "%s: inv[%d] = %g is not finite", who, a, g.inv[a]);
-        if (!(g.inv[a] > 0.0)) return pfail(NCA_E_INVALID, "%s: inv[%d] = %g is not positive", who, a, g.inv[a]);
-    }
-    // n0 n1 < 2^62 always; the bytes of all phases must fit int64
-    const int64_t n01 = (int64_t)g.n[0] * g.n[1];
-    if (n01 > (INT64_MAX / 4 / n_phase) / g.n[2])
-        return pfail(NCA_E_INVALID, "%s: %d phases of %d x %d x %d voxels overflow int64", who, (int)n_phase, (int)g.n[0], (int)g.n[1], (int)g.n[2]);
-    const int64_t voxels = n01 * g.n[2];
-    const int tile[3] = {PH_T0, PH_T1, PH_T2};
+    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    NCA_REFUSE_NULL(g_err, who, out);
+    if (n_phase <= 0) return g_err.fail(NCA_E_INVALID, "%s: n_phase = %d is not positive", who, (int)n_phase);
+    if (n_ell < 0) return g_err.fail(NCA_E_INVALID, "%s: n_ell = %d is negative", who, (int)n_ell);
+    if (n_seg < 0) return g_err.fail(NCA_E_INVALID, "%s: n_seg = %d is negative", who, (int)n_seg);
+    if (n_ell == 0 && n_seg == 0) return g_err.fail(NCA_E_INVALID, "%s: n_ell = 0 and n_seg = 0: there is nothing to rasterise", who);
+    if (n_ell > 0 && !ell) return g_err.fail(NCA_E_INVALID, "%s: ell is NULL with n_ell = %d", who, (int)n_ell);
+    if (n_seg > 0 && !seg) return g_err.fail(NCA_E_INVALID, "%s: seg is NULL with n_seg = %d", who, (int)n_seg);
+    if (!(isfinite(edge) && edge > 0.0)) return g_err.fail(NCA_E_INVALID, "%s: edge = %g is not finite and positive", who, edge);
+    if (!isfinite(rho_v)) return g_err.fail(NCA_E_INVALID, "%s: rho_v = %g is not finite", who, rho_v);
+    NcaGrid g;
+    int64_t voxels, tiles;
     int32_t nb[3];
-    for (int a = 0; a < 3; ++a) nb[a] = (int32_t)(((int64_t)g.n[a] + tile[a] - 1) / tile[a]);
-    const int64_t tiles = (int64_t)nb[0] * nb[1] * nb[2];          // at most the voxel count: no overflow
-    if (tiles > 0x7fffffffLL / n_phase)
-        return pfail(NCA_E_INVALID, "%s: %d phases of %d x %d x %d voxels make %lld x %d tiles, more than one launch covers", who, (int)n_phase, (int)g.n[0],
-                     (int)g.n[1], (int)g.n[2], (long long)tiles, (int)n_phase);
+    int rc = nca_check_grid(g_err, who, grid, n_phase, 4, "phases", &g, &voxels);
+    if (rc == NCA_OK) rc = nca_count_tiles(g_err, who, g, n_phase, nb, &tiles);
+    if (rc != NCA_OK) return rc;
     const dim3 blocks((unsigned)(tiles * n_phase)), threads(PH_BLOCK);
     if (g_ph_cull.load())
         hipLaunchKernelGGL((phantom_kernel<true>), blocks, threads, 0, (hipStream_t)stream, g, voxels, tiles, nb[1], nb[2], n_ell, ell, n_seg, seg, rho_v, edge, out);
     else
         hipLaunchKernelGGL((phantom_kernel<false>), blocks, threads, 0, (hipStream_t)stream, g, voxels, tiles, nb[1], nb[2], n_ell, ell, n_seg, seg, rho_v, edge, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return pfail(NCA_E_HIP, "%s: %s", who, hipGetErrorString(e));
-    return NCA_OK;
+    return nca_launched(g_err, who);
 }

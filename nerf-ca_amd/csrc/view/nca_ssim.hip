@@ -2,25 +2,12 @@
 // metrics.ssim / compare_sequences and the ssim_weight of drr.fit_volumes.  The value is one pass over the two stacks (plus tile halos); the
 // gradient stages its three coefficient maps P, Q, R in the caller's workspace and gathers them -- every pixel is written once by one
 // thread, no atomics.  This translation unit keeps its own thread-local error message (nca_ssim_last_error): it shares no state with the
-// other sections.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdint.h>
-#include "../../../include/nerfca_hip.h"
+// other sections.  The workspace refusal and the launch epilogue are nca_view_common.hpp's.
+#include "nca_view_common.hpp"
 
-static thread_local char g_ssim_err[256] = "";
+static thread_local NcaViewErr g_err;
 
-static int sfail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_ssim_err, sizeof(g_ssim_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-extern "C" const char* nca_ssim_last_error(void) { return g_ssim_err; }
+extern "C" const char* nca_ssim_last_error(void) { return g_err.msg; }
 
 // A workgroup of four waves owns a tile of 16 x 32: window positions in ssim_kernel, pixels in ssim_gather_kernel.  Thread t takes the
 // column t & 31 and the rows (t >> 5) and (t >> 5) + 8.  The window length is a template argument, so the weights are kernel arguments
@@ -223,19 +210,19 @@ __global__ void __launch_bounds__(SS_BLOCK) ssim_gather_kernel(int32_t H, int32_
 // window positions / of the pixels, all images together; the pixels' count is the larger one and is the one held to a launch's limit.
 static int ssim_check(const char* who, int32_t N, int32_t H, int32_t W, int32_t K, const double* win, double k1, double k2, int32_t nbv[2], int32_t nbp[2],
                       int64_t* blocks_v, int64_t* blocks_p) {
-    if (N <= 0) return sfail(NCA_E_INVALID, "%s: N = %d is not positive", who, (int)N);
-    if (H <= 0) return sfail(NCA_E_INVALID, "%s: H = %d is not positive", who, (int)H);
-    if (W <= 0) return sfail(NCA_E_INVALID, "%s: W = %d is not positive", who, (int)W);
-    if (K < 1 || K > NCA_SSIM_MAX_WIN || K % 2 == 0) return sfail(NCA_E_INVALID, "%s: K = %d is not an odd window length in [1, %d]", who, (int)K, (int)NCA_SSIM_MAX_WIN);
-    if (H < K) return sfail(NCA_E_INVALID, "%s: H = %d is smaller than the window, K = %d", who, (int)H, (int)K);
-    if (W < K) return sfail(NCA_E_INVALID, "%s: W = %d is smaller than the window, K = %d", who, (int)W, (int)K);
+    if (N <= 0) return g_err.fail(NCA_E_INVALID, "%s: N = %d is not positive", who, (int)N);
+    if (H <= 0) return g_err.fail(NCA_E_INVALID, "%s: H = %d is not positive", who, (int)H);
+    if (W <= 0) return g_err.fail(NCA_E_INVALID, "%s: W = %d is not positive", who, (int)W);
+    if (K < 1 || K > NCA_SSIM_MAX_WIN || K % 2 == 0) return g_err.fail(NCA_E_INVALID, "%s: K = %d is not an odd window length in [1, %d]", who, (int)K, (int)NCA_SSIM_MAX_WIN);
+    if (H < K) return g_err.fail(NCA_E_INVALID, "%s: H = %d is smaller than the window, K = %d", who, (int)H, (int)K);
+    if (W < K) return g_err.fail(NCA_E_INVALID, "%s: W = %d is smaller than the window, K = %d", who, (int)W, (int)K);
     if (win)
         for (int a = 0; a < K; ++a)
-            if (!isfinite(win[a])) return sfail(NCA_E_INVALID, "%s: win[%d] = %g is not finite", who, a, win[a]);
-    if (!(isfinite(k1) && k1 > 0.0)) return sfail(NCA_E_INVALID, "%s: k1 = %g is not finite and positive", who, k1);
-    if (!(isfinite(k2) && k2 > 0.0)) return sfail(NCA_E_INVALID, "%s: k2 = %g is not finite and positive", who, k2);
+            if (!isfinite(win[a])) return g_err.fail(NCA_E_INVALID, "%s: win[%d] = %g is not finite", who, a, win[a]);
+    if (!(isfinite(k1) && k1 > 0.0)) return g_err.fail(NCA_E_INVALID, "%s: k1 = %g is not finite and positive", who, k1);
+    if (!(isfinite(k2) && k2 > 0.0)) return g_err.fail(NCA_E_INVALID, "%s: k2 = %g is not finite and positive", who, k2);
     // H W < 2^62 always; the 24 bytes per position of the coefficient maps (and the 4 per pixel) must fit int64
-    if ((int64_t)H * W > INT64_MAX / 32 / N) return sfail(NCA_E_INVALID, "%s: %d images of %d x %d pixels overflow int64", who, (int)N, (int)H, (int)W);
+    if ((int64_t)H * W > INT64_MAX / 32 / N) return g_err.fail(NCA_E_INVALID, "%s: %d images of %d x %d pixels overflow int64", who, (int)N, (int)H, (int)W);
     const int32_t Hv = H - K + 1, Wv = W - K + 1;
     nbv[0] = (int32_t)(((int64_t)Hv + SS_TH - 1) / SS_TH), nbv[1] = (int32_t)(((int64_t)Wv + SS_TW - 1) / SS_TW);
     nbp[0] = (int32_t)(((int64_t)H + SS_TH - 1) / SS_TH), nbp[1] = (int32_t)(((int64_t)W + SS_TW - 1) / SS_TW);
@@ -243,7 +230,7 @@ static int ssim_check(const char* who, int32_t N, int32_t H, int32_t W, int32_t 
     *blocks_p = (int64_t)N * nbp[0] * nbp[1];
     // a launch carries at most 2^32 threads (the runtime rejects gridDim.x * blockDim.x beyond that): 2^24 workgroups of 256
     if (*blocks_p > SS_MAX_BLOCKS)
-        return sfail(NCA_E_INVALID, "%s: %d images of %d x %d pixels make %lld tiles, more than one launch covers", who, (int)N, (int)H, (int)W, (long long)*blocks_p);
+        return g_err.fail(NCA_E_INVALID, "%s: %d images of %d x %d pixels make %lld tiles, more than one launch covers", who, (int)N, (int)H, (int)W, (long long)*blocks_p);
     return NCA_OK;
 }
 
@@ -267,20 +254,18 @@ static SsimWin<K> pack_win(const double* win) {
 extern "C" int nca_ssim(int32_t N, int32_t H, int32_t W, const float* x, const float* y, const double* range, int32_t K, const double* win, double k1, double k2,
                         double* sum, float* map, void* stream) {
     const char* who = "nca_ssim";
-    if (!x) return sfail(NCA_E_INVALID, "%s: x is NULL", who);
-    if (!y) return sfail(NCA_E_INVALID, "%s: y is NULL", who);
-    if (!range) return sfail(NCA_E_INVALID, "%s: range is NULL", who);
-    if (!win) return sfail(NCA_E_INVALID, "%s: win is NULL", who);
-    if (!sum) return sfail(NCA_E_INVALID, "%s: sum is NULL", who);
+    NCA_REFUSE_NULL(g_err, who, x);
+    NCA_REFUSE_NULL(g_err, who, y);
+    NCA_REFUSE_NULL(g_err, who, range);
+    NCA_REFUSE_NULL(g_err, who, win);
+    NCA_REFUSE_NULL(g_err, who, sum);
     int32_t nbv[2], nbp[2];
     int64_t blocks_v, blocks_p;
     const int rc = ssim_check(who, N, H, W, K, win, k1, k2, nbv, nbp, &blocks_v, &blocks_p);
     if (rc != NCA_OK) return rc;
     SS_DISPATCH(K, hipLaunchKernelGGL((ssim_kernel<KK, false>), dim3((unsigned)blocks_v), dim3(SS_BLOCK), 0, (hipStream_t)stream, H, W, nbv[0], nbv[1], x, y, range,
                                       pack_win<KK>(win), k1, k2, sum, map, (double*)nullptr, (int64_t)0));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return sfail(NCA_E_HIP, "%s: %s", who, hipGetErrorString(e));
-    return NCA_OK;
+    return nca_launched(g_err, who);
 }
 
 extern "C" size_t nca_ssim_grad_workspace(int32_t N, int32_t H, int32_t W, int32_t K) {
@@ -292,20 +277,18 @@ extern "C" size_t nca_ssim_grad_workspace(int32_t N, int32_t H, int32_t W, int32
 extern "C" int nca_ssim_grad(int32_t N, int32_t H, int32_t W, const float* x, const float* y, const double* range, int32_t K, const double* win, double k1, double k2,
                              const double* scale, float* g_x, void* work, size_t work_bytes, void* stream) {
     const char* who = "nca_ssim_grad";
-    if (!x) return sfail(NCA_E_INVALID, "%s: x is NULL", who);
-    if (!y) return sfail(NCA_E_INVALID, "%s: y is NULL", who);
-    if (!range) return sfail(NCA_E_INVALID, "%s: range is NULL", who);
-    if (!win) return sfail(NCA_E_INVALID, "%s: win is NULL", who);
-    if (!scale) return sfail(NCA_E_INVALID, "%s: scale is NULL", who);
-    if (!g_x) return sfail(NCA_E_INVALID, "%s: g_x is NULL", who);
+    NCA_REFUSE_NULL(g_err, who, x);
+    NCA_REFUSE_NULL(g_err, who, y);
+    NCA_REFUSE_NULL(g_err, who, range);
+    NCA_REFUSE_NULL(g_err, who, win);
+    NCA_REFUSE_NULL(g_err, who, scale);
+    NCA_REFUSE_NULL(g_err, who, g_x);
     int32_t nbv[2], nbp[2];
     int64_t blocks_v, blocks_p;
     const int rc = ssim_check(who, N, H, W, K, win, k1, k2, nbv, nbp, &blocks_v, &blocks_p);
     if (rc != NCA_OK) return rc;
-    const size_t need = nca_ssim_grad_workspace(N, H, W, K);
-    if (!work || work_bytes < need)
-        return sfail(NCA_E_WORKSPACE, "%s: the workspace holds %llu bytes%s, %llu are needed", who, (unsigned long long)work_bytes, work ? "" : " (work is NULL)",
-                     (unsigned long long)need);
+    const int rcw = nca_check_workspace(g_err, who, work, work_bytes, nca_ssim_grad_workspace(N, H, W, K));
+    if (rcw != NCA_OK) return rcw;
     const int64_t plane = (int64_t)N * (H - K + 1) * (W - K + 1);
     double* coef = (double*)work;
     SS_DISPATCH(K, {
@@ -315,7 +298,5 @@ extern "C" int nca_ssim_grad(int32_t N, int32_t H, int32_t W, const float* x, co
         hipLaunchKernelGGL((ssim_gather_kernel<KK>), dim3((unsigned)blocks_p), dim3(SS_BLOCK), 0, (hipStream_t)stream, H, W, nbp[0], nbp[1], x, y,
                            (const double*)coef, plane, w, scale, g_x);
     });
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return sfail(NCA_E_HIP, "%s: %s", who, hipGetErrorString(e));
-    return NCA_OK;
+    return nca_launched(g_err, who);
 }

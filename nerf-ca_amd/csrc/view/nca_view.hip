@@ -2,31 +2,13 @@
 // device, the composition of two single-field renders into the three images the reference's display block logs, and the per-image
 // min / max normalisation it applies before logging (train/run_composite.py:361, 405-413).  Forward only, no MLP here: the static
 // field is rendered by nca_render_fwd in single-field mode, the dynamic field by nca_mlp_fwd on the query points made here and
-// nca_composite_fwd.  This translation unit keeps its own thread-local error message
-// (nca_view_last_error): it shares no state with nca_api.hip.
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdint.h>
-#include "../../../include/nerfca_hip.h"
+// nca_composite_fwd.  This translation unit keeps its own thread-local error message (nca_view_last_error): it shares no state with
+// nca_api.hip or the other sections; the message type and the launch epilogue are nca_view_common.hpp's.
+#include "nca_view_common.hpp"
 
-static thread_local char g_view_err[256] = "";
+static thread_local NcaViewErr g_err;
 
-static int vfail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_view_err, sizeof(g_view_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-static int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return vfail(NCA_E_HIP, "%s: %s", what, hipGetErrorString(e));
-    return NCA_OK;
-}
-
-extern "C" const char* nca_view_last_error(void) { return g_view_err; }
+extern "C" const char* nca_view_last_error(void) { return g_err.msg; }
 
 constexpr int VIEW_BLOCK = 256;
 
@@ -53,22 +35,22 @@ __global__ void __launch_bounds__(VIEW_BLOCK) view_rays_kernel(NcaView v, int64_
 }
 
 extern "C" int nca_view_rays(const NcaView* view, int64_t p0, int64_t n, int32_t out_f64, void* origins, void* dirs, void* stream) {
-    if (!view) return vfail(NCA_E_INVALID, "nca_view_rays: the view descriptor is NULL");
-    if (view->W <= 0 || view->H <= 0) return vfail(NCA_E_INVALID, "nca_view_rays: detector %d x %d is not positive", (int)view->W, (int)view->H);
-    if (n <= 0) return vfail(NCA_E_INVALID, "nca_view_rays: n = %lld is not positive", (long long)n);
-    if (p0 < 0) return vfail(NCA_E_INVALID, "nca_view_rays: p0 = %lld is negative", (long long)p0);
+    if (!view) return g_err.fail(NCA_E_INVALID, "nca_view_rays: the view descriptor is NULL");
+    if (view->W <= 0 || view->H <= 0) return g_err.fail(NCA_E_INVALID, "nca_view_rays: detector %d x %d is not positive", (int)view->W, (int)view->H);
+    if (n <= 0) return g_err.fail(NCA_E_INVALID, "nca_view_rays: n = %lld is not positive", (long long)n);
+    if (p0 < 0) return g_err.fail(NCA_E_INVALID, "nca_view_rays: p0 = %lld is negative", (long long)p0);
     const int64_t npix = (int64_t)view->W * view->H;
     if (p0 > npix || n > npix - p0)
-        return vfail(NCA_E_INVALID, "nca_view_rays: pixels [%lld, %lld + %lld) leave the %lld of the detector", (long long)p0, (long long)p0, (long long)n, (long long)npix);
-    if (!origins || !dirs) return vfail(NCA_E_INVALID, "nca_view_rays: an output pointer is NULL");
+        return g_err.fail(NCA_E_INVALID, "nca_view_rays: pixels [%lld, %lld + %lld) leave the %lld of the detector", (long long)p0, (long long)p0, (long long)n, (long long)npix);
+    if (!origins || !dirs) return g_err.fail(NCA_E_INVALID, "nca_view_rays: an output pointer is NULL");
     const int64_t blocks = (n + VIEW_BLOCK - 1) / VIEW_BLOCK;
-    if (blocks > 0x7fffffffLL) return vfail(NCA_E_INVALID, "nca_view_rays: n = %lld is more than one launch covers", (long long)n);
+    if (blocks > 0x7fffffffLL) return g_err.fail(NCA_E_INVALID, "nca_view_rays: n = %lld is more than one launch covers", (long long)n);
     const dim3 grid((unsigned)blocks);
     if (out_f64)
         hipLaunchKernelGGL(view_rays_kernel<double>, grid, dim3(VIEW_BLOCK), 0, (hipStream_t)stream, *view, p0, n, (double*)origins, (double*)dirs);
     else
         hipLaunchKernelGGL(view_rays_kernel<float>, grid, dim3(VIEW_BLOCK), 0, (hipStream_t)stream, *view, p0, n, (float*)origins, (float*)dirs);
-    return launched("nca_view_rays");
+    return nca_launched(g_err, "nca_view_rays");
 }
 
 // ---- query points of a ray chunk ----------------------------------------------------------------------------------------------------
@@ -87,15 +69,15 @@ __global__ void __launch_bounds__(VIEW_BLOCK) view_points_kernel(int64_t total, 
 }
 
 extern "C" int nca_view_points(int64_t R, int32_t S, const double* origins, const double* dirs, const float* z, float* pts, void* stream) {
-    if (R <= 0 || S <= 0) return vfail(NCA_E_INVALID, "nca_view_points: %lld rays x %d samples is not positive", (long long)R, (int)S);
-    if (!origins || !dirs || !z) return vfail(NCA_E_INVALID, "nca_view_points: an input pointer is NULL");
-    if (!pts) return vfail(NCA_E_INVALID, "nca_view_points: the output pointer is NULL");
-    if (R > (INT64_MAX / 3) / S) return vfail(NCA_E_INVALID, "nca_view_points: %lld rays x %d samples overflows", (long long)R, (int)S);
+    if (R <= 0 || S <= 0) return g_err.fail(NCA_E_INVALID, "nca_view_points: %lld rays x %d samples is not positive", (long long)R, (int)S);
+    if (!origins || !dirs || !z) return g_err.fail(NCA_E_INVALID, "nca_view_points: an input pointer is NULL");
+    if (!pts) return g_err.fail(NCA_E_INVALID, "nca_view_points: the output pointer is NULL");
+    if (R > (INT64_MAX / 3) / S) return g_err.fail(NCA_E_INVALID, "nca_view_points: %lld rays x %d samples overflows", (long long)R, (int)S);
     const int64_t total = R * S * 3, blocks = (total + VIEW_BLOCK - 1) / VIEW_BLOCK;
-    if (blocks > 0x7fffffffLL) return vfail(NCA_E_INVALID, "nca_view_points: %lld rays x %d samples is more than one launch covers", (long long)R, (int)S);
+    if (blocks > 0x7fffffffLL) return g_err.fail(NCA_E_INVALID, "nca_view_points: %lld rays x %d samples is more than one launch covers", (long long)R, (int)S);
     const dim3 grid((unsigned)blocks);
     hipLaunchKernelGGL(view_points_kernel, grid, dim3(VIEW_BLOCK), 0, (hipStream_t)stream, total, S, origins, dirs, z, pts);
-    return launched("nca_view_points");
+    return nca_launched(g_err, "nca_view_points");
 }
 
 // ---- composite / static / dynamic image from two single-field renders ------------------------------------------------------------
@@ -121,11 +103,11 @@ __global__ void __launch_bounds__(VIEW_BLOCK) view_compose_kernel(int64_t n, dou
 
 extern "C" int nca_view_compose(int64_t n, double i0, const void* pix_s, const void* pix_d, int32_t pix_is_f64, float* pred, float* pred_s,
                                 float* pred_d, void* stream) {
-    if (n <= 0) return vfail(NCA_E_INVALID, "nca_view_compose: n = %lld is not positive", (long long)n);
-    if (!pix_s) return vfail(NCA_E_INVALID, "nca_view_compose: pix_s is NULL");
-    if (!pred || !pred_s || !pred_d) return vfail(NCA_E_INVALID, "nca_view_compose: an output pointer is NULL");
+    if (n <= 0) return g_err.fail(NCA_E_INVALID, "nca_view_compose: n = %lld is not positive", (long long)n);
+    if (!pix_s) return g_err.fail(NCA_E_INVALID, "nca_view_compose: pix_s is NULL");
+    if (!pred || !pred_s || !pred_d) return g_err.fail(NCA_E_INVALID, "nca_view_compose: an output pointer is NULL");
     const int64_t blocks = (n + VIEW_BLOCK - 1) / VIEW_BLOCK;
-    if (blocks > 0x7fffffffLL) return vfail(NCA_E_INVALID, "nca_view_compose: n = %lld is more than one launch covers", (long long)n);
+    if (blocks > 0x7fffffffLL) return g_err.fail(NCA_E_INVALID, "nca_view_compose: n = %lld is more than one launch covers", (long long)n);
     const dim3 grid((unsigned)blocks);
     if (pix_is_f64)
         hipLaunchKernelGGL(view_compose_kernel<double>, grid, dim3(VIEW_BLOCK), 0, (hipStream_t)stream, n, i0, (const double*)pix_s, (const double*)pix_d,
@@ -133,7 +115,7 @@ extern "C" int nca_view_compose(int64_t n, double i0, const void* pix_s, const v
     else
         hipLaunchKernelGGL(view_compose_kernel<float>, grid, dim3(VIEW_BLOCK), 0, (hipStream_t)stream, n, i0, (const float*)pix_s, (const float*)pix_d,
                            pred, pred_s, pred_d);
-    return launched("nca_view_compose");
+    return nca_launched(g_err, "nca_view_compose");
 }
 
 // ---- per-image min / max and (x - min) / (max - min) -----------------------------------------------------------------------------
@@ -202,25 +184,25 @@ __global__ void __launch_bounds__(VIEW_BLOCK) norm_scale_kernel(int64_t n, const
 }
 
 extern "C" int64_t nca_image_normalize_workspace(int64_t n) {
-    if (n <= 0) return vfail(NCA_E_INVALID, "nca_image_normalize_workspace: n = %lld is not positive", (long long)n);
+    if (n <= 0) return g_err.fail(NCA_E_INVALID, "nca_image_normalize_workspace: n = %lld is not positive", (long long)n);
     const int64_t bytes = norm_blocks(n) * (int64_t)sizeof(float2);
     return (bytes + 255) / 256 * 256;
 }
 
 extern "C" int nca_image_normalize(int32_t n_img, int64_t n, const float* img, float* out, float* minmax, void* work, int64_t work_bytes, void* stream) {
-    if (n_img <= 0) return vfail(NCA_E_INVALID, "nca_image_normalize: n_img = %d is not positive", (int)n_img);
-    if (n_img > 65535) return vfail(NCA_E_INVALID, "nca_image_normalize: n_img = %d is more than 65535 images a call", (int)n_img);
-    if (n <= 0) return vfail(NCA_E_INVALID, "nca_image_normalize: n = %lld is not positive", (long long)n);
-    if (!img) return vfail(NCA_E_INVALID, "nca_image_normalize: img is NULL");
-    if (!minmax) return vfail(NCA_E_INVALID, "nca_image_normalize: minmax is NULL");
+    if (n_img <= 0) return g_err.fail(NCA_E_INVALID, "nca_image_normalize: n_img = %d is not positive", (int)n_img);
+    if (n_img > 65535) return g_err.fail(NCA_E_INVALID, "nca_image_normalize: n_img = %d is more than 65535 images a call", (int)n_img);
+    if (n <= 0) return g_err.fail(NCA_E_INVALID, "nca_image_normalize: n = %lld is not positive", (long long)n);
+    if (!img) return g_err.fail(NCA_E_INVALID, "nca_image_normalize: img is NULL");
+    if (!minmax) return g_err.fail(NCA_E_INVALID, "nca_image_normalize: minmax is NULL");
     const int64_t need = (int64_t)n_img * nca_image_normalize_workspace(n);
     if (!work || work_bytes < need)
-        return vfail(NCA_E_WORKSPACE, "nca_image_normalize: workspace of %lld bytes, %lld needed (n_img x nca_image_normalize_workspace)", (long long)(work ? work_bytes : 0),
+        return g_err.fail(NCA_E_WORKSPACE, "nca_image_normalize: workspace of %lld bytes, %lld needed (n_img x nca_image_normalize_workspace)", (long long)(work ? work_bytes : 0),
                      (long long)need);
     const int32_t blocks = (int32_t)norm_blocks(n);
     float2* part = (float2*)work;
     hipLaunchKernelGGL(norm_partial_kernel, dim3(blocks, n_img), dim3(VIEW_BLOCK), 0, (hipStream_t)stream, n, blocks, img, part);
     hipLaunchKernelGGL(norm_finish_kernel, dim3(n_img), dim3(VIEW_BLOCK), 0, (hipStream_t)stream, blocks, (const float2*)part, minmax);
     if (out) hipLaunchKernelGGL(norm_scale_kernel, dim3(blocks, n_img), dim3(VIEW_BLOCK), 0, (hipStream_t)stream, n, img, (const float*)minmax, out);
-    return launched("nca_image_normalize");
+    return nca_launched(g_err, "nca_image_normalize");
 }

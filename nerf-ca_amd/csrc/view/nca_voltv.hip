@@ -1,32 +1,17 @@
 // nca_voltv.hip -- smoothed total variation of voxel volumes in space and along the heart phase (include/nerfca_hip.h, "vol"): the two
 // priors drr.fit_volumes adds to its data term, and their gradient (drr.total_variation).  Both kernels are one read of the volumes (plus
 // tile halos); the gradient is gathered -- every node is written once by one thread, no atomics -- and writes one f32 per node.  This
-// translation unit keeps its own thread-local error message (nca_vol_last_error): it shares no state with the other sections.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdint.h>
-#include "../../../include/nerfca_hip.h"
+// translation unit keeps its own thread-local error message (nca_vol_last_error): it shares no state with the other sections.  The grid
+// checks, the tile count and the tile's indexing are nca_view_common.hpp's.
+#include "nca_view_common.hpp"
 
-static thread_local char g_vol_err[256] = "";
+static thread_local NcaViewErr g_err;
 
-static int vfail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_vol_err, sizeof(g_vol_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+extern "C" const char* nca_vol_last_error(void) { return g_err.msg; }
 
-extern "C" const char* nca_vol_last_error(void) { return g_vol_err; }
-
-// A workgroup owns a tile of 4 x 8 x 64 nodes of the grid and marches it through the volumes p = 0 .. n_vol-1.  Wave w of the eight takes the
-// rows (j0, j1) = (k, w), k = 0 .. 3, with its 64 lanes along the last (contiguous) axis: 4 nodes per thread.
-constexpr int TV_T0 = 4, TV_T1 = 8, TV_T2 = 64;
-constexpr int TV_BLOCK = 512, TV_WAVES = TV_BLOCK / 64;
-constexpr int TV_NPT = TV_T0 * TV_T1 * TV_T2 / TV_BLOCK;
-static_assert(TV_T2 == 64 && TV_WAVES == TV_T1 && TV_NPT == TV_T0, "a wave is one row of the tile: node k of a thread is (k, wave, lane)");
+// A workgroup owns a tile of 4 x 8 x 64 nodes of the grid (nca_view_common.hpp) and marches it through the volumes p = 0 .. n_vol-1.
+constexpr int TV_T0 = NCA_TILE0, TV_T1 = NCA_TILE1, TV_T2 = NCA_TILE2;
+constexpr int TV_BLOCK = NCA_TILE_BLOCK, TV_WAVES = NCA_TILE_WAVES, TV_NPT = NCA_TILE_NPT;
 
 // sqrt(e2 + t t) of one phase pair
 __device__ __forceinline__ double tv_mt(double e2, double t) { return __dsqrt_rn(__dadd_rn(e2, __dmul_rn(t, t))); }
@@ -53,8 +38,8 @@ __global__ void __launch_bounds__(TV_BLOCK) voltv_kernel(NcaGrid g, const float*
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);          // the wave's number, known to be uniform
     const int32_t n0 = g.n[0], n1 = g.n[1], n2 = g.n[2];
     const double inv0 = g.inv[0], inv1 = g.inv[1], inv2 = g.inv[2];
-    const int64_t bid = blockIdx.x;
-    const int32_t base2 = (int32_t)(bid % nb2) * TV_T2, base1 = (int32_t)((bid / nb2) % nb1) * TV_T1, base0 = (int32_t)(bid / ((int64_t)nb2 * nb1)) * TV_T0;
+    const NcaTile tile = nca_tile(blockIdx.x, nb1, nb2);
+    const int32_t base0 = tile.base0, base1 = tile.base1, base2 = tile.base2;
     const double es2 = __dmul_rn(eps_s, eps_s), et2 = __dmul_rn(eps_t, eps_t);
     const bool wrap = cyclic != 0 && n_vol >= 2;
 
@@ -69,20 +54,17 @@ __global__ void __launch_bounds__(TV_BLOCK) voltv_kernel(NcaGrid g, const float*
     };
 
     // the thread's own nodes: (j0, j1, j2) = (k, wave, lane)
-    const int32_t i2 = base2 + lane;
-    const bool ok12 = i2 < n2 && base1 + wave < n1;
-    const int64_t off_t = ((int64_t)base0 * n1 + (base1 + wave)) * n2 + i2;
-    auto live_at = [&](int k) -> bool { return ok12 && base0 + k < n0; };
-    auto off_at = [&](int k) -> int64_t { return off_t + (int64_t)k * n1 * n2; };          // used only where live
+    const NcaTileNodes nodes = nca_tile_nodes(tile, wave, lane, n0, n1, n2);
+    const int32_t i2 = nodes.i2;
     float xc[TV_NPT], xn[TV_NPT];
     double qp[GRAD ? TV_NPT : 1];          // t / mt of the pair that ends at the current volume, 0 where there is none
 #pragma unroll
     for (int k = 0; k < TV_NPT; ++k) {
-        xn[k] = live_at(k) ? vol[off_at(k)] : 0.0f;
+        xn[k] = nodes.live(k) ? vol[nodes.off(k)] : 0.0f;
         if constexpr (GRAD) {
             qp[k] = 0.0;
-            if (wrap && live_at(k)) {
-                const double t = __dsub_rn((double)xn[k], (double)vol[(int64_t)(n_vol - 1) * voxels + off_at(k)]);
+            if (wrap && nodes.live(k)) {
+                const double t = __dsub_rn((double)xn[k], (double)vol[(int64_t)(n_vol - 1) * voxels + nodes.off(k)]);
                 qp[k] = __ddiv_rn(t, tv_mt(et2, t));
             }
         }
@@ -98,7 +80,7 @@ __global__ void __launch_bounds__(TV_BLOCK) voltv_kernel(NcaGrid g, const float*
 #pragma unroll
         for (int k = 0; k < TV_NPT; ++k) {
             xc[k] = xn[k];
-            if (pair) xn[k] = live_at(k) ? nxt[off_at(k)] : 0.0f;
+            if (pair) xn[k] = nodes.live(k) ? nxt[nodes.off(k)] : 0.0f;
         }
         __syncthreads();          // the previous volume's readers are done with s_x and s_m
 #pragma unroll
@@ -126,7 +108,7 @@ __global__ void __launch_bounds__(TV_BLOCK) voltv_kernel(NcaGrid g, const float*
         }
 #pragma unroll
         for (int k = 0; k < TV_NPT; ++k) {
-            if (!live_at(k)) continue;
+            if (!nodes.live(k)) continue;
             const int j0 = k, j1 = wave;
             const int32_t i0 = base0 + j0, i1 = base1 + j1;
             const double t = __dsub_rn((double)xn[k], (double)xc[k]);              // used only where the pair exists
@@ -150,7 +132,7 @@ __global__ void __launch_bounds__(TV_BLOCK) voltv_kernel(NcaGrid g, const float*
                 const double q = pair ? __ddiv_rn(t, tv_mt(et2, t)) : 0.0;
                 const double gt = __dadd_rn(-q, qp[k]);
                 qp[k] = q;
-                g_vol[(int64_t)p * voxels + off_at(k)] = (float)__dadd_rn(__dmul_rn(s0, gs), __dmul_rn(s1, gt));
+                g_vol[(int64_t)p * voxels + nodes.off(k)] = (float)__dadd_rn(__dmul_rn(s0, gs), __dmul_rn(s1, gt));
             }
         }
     }
@@ -172,63 +154,43 @@ __global__ void __launch_bounds__(TV_BLOCK) voltv_kernel(NcaGrid g, const float*
     }
 }
 
-// The checks both entry points share; on success *voxels and the blocks per axis are set.
+// The checks both entry points share, after their own pointers; on success *voxels and the tiles per axis are set.
 static int vol_check(const char* who, const NcaGrid* grid, const float* vol, int32_t n_vol, double eps_s, double eps_t, int32_t cyclic, NcaGrid* g,
-                     int64_t* voxels, int32_t nb[3]) {
-    if (!grid) return vfail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
-    if (!vol) return vfail(NCA_E_INVALID, "%s: vol is NULL", who);
-    if (n_vol <= 0) return vfail(NCA_E_INVALID, "%s: n_vol = %d is not positive", who, (int)n_vol);
-    if (cyclic != 0 && cyclic != 1) return vfail(NCA_E_INVALID, "%s: cyclic = %d is neither 0 nor 1", who, (int)cyclic);
-    if (!(isfinite(eps_s) && eps_s > 0.0)) return vfail(NCA_E_INVALID, "%s: eps_s = %g is not finite and positive", who, eps_s);
-    if (!(isfinite(eps_t) && eps_t > 0.0)) return vfail(NCA_E_INVALID, "%s: eps_t = %g is not finite and positive", who, eps_t);
-    *g = *grid;
-    if (g->reserved != 0) return vfail(NCA_E_INVALID, "%s: reserved = %d is not 0", who, (int)g->reserved);
-    for (int a = 0; a < 3; ++a) {
-        if (g->n[a] < 2) return vfail(NCA_E_INVALID, "%s: n[%d] = %d is less than 2 nodes", who, a, (int)g->n[a]);
-        if (!isfinite(g->lo[a])) return vfail(NCA_E_INVALID, "%s: lo[%d] = %g is not finite", who, a, g->lo[a]);
-        if (!isfinite(g->inv[a])) return vfail(NCA_E_INVALID, "%s: inv[%d] = %g is not finite", who, a, g->inv[a]);
-        if (!(g->inv[a] > 0.0)) return vfail(NCA_E_INVALID, "%s: inv[%d] = %g is not positive", who, a, g->inv[a]);
-    }
-    // n0 n1 < 2^62 always; the bytes of all volumes must fit int64
-    const int64_t n01 = (int64_t)g->n[0] * g->n[1];
-    if (n01 > (INT64_MAX / 4 / n_vol) / g->n[2])
-        return vfail(NCA_E_INVALID, "%s: %d volumes of %d x %d x %d voxels overflow int64", who, (int)n_vol, (int)g->n[0], (int)g->n[1], (int)g->n[2]);
-    *voxels = n01 * g->n[2];
-    const int tile[3] = {TV_T0, TV_T1, TV_T2};
-    for (int a = 0; a < 3; ++a) nb[a] = (int32_t)(((int64_t)g->n[a] + tile[a] - 1) / tile[a]);
-    const int64_t blocks = (int64_t)nb[0] * nb[1] * nb[2];          // at most the voxel count: no overflow
-    if (blocks > 0x7fffffffLL)
-        return vfail(NCA_E_INVALID, "%s: %d x %d x %d voxels make %lld tiles, more than one launch covers", who, (int)g->n[0], (int)g->n[1], (int)g->n[2],
-                     (long long)blocks);
-    return NCA_OK;
+                     int64_t* voxels, int32_t nb[3], int64_t* tiles) {
+    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    NCA_REFUSE_NULL(g_err, who, vol);
+    if (n_vol <= 0) return g_err.fail(NCA_E_INVALID, "%s: n_vol = %d is not positive", who, (int)n_vol);
+    if (cyclic != 0 && cyclic != 1) return g_err.fail(NCA_E_INVALID, "%s: cyclic = %d is neither 0 nor 1", who, (int)cyclic);
+    if (!(isfinite(eps_s) && eps_s > 0.0)) return g_err.fail(NCA_E_INVALID, "%s: eps_s = %g is not finite and positive", who, eps_s);
+    if (!(isfinite(eps_t) && eps_t > 0.0)) return g_err.fail(NCA_E_INVALID, "%s: eps_t = %g is not finite and positive", who, eps_t);
+    const int rc = nca_check_grid(g_err, who, grid, n_vol, 4, "volumes", g, voxels);
+    return rc != NCA_OK ? rc : nca_count_tiles(g_err, who, *g, 0, nb, tiles);
 }
 
 extern "C" int nca_vol_tv(const NcaGrid* grid, const float* vol, int32_t n_vol, double eps_s, double eps_t, int32_t cyclic, double* out, void* stream) {
+    const char* who = "nca_vol_tv";
     NcaGrid g;
-    int64_t voxels;
+    int64_t voxels, tiles;
     int32_t nb[3];
-    if (!out) return vfail(NCA_E_INVALID, "nca_vol_tv: out is NULL");
-    const int rc = vol_check("nca_vol_tv", grid, vol, n_vol, eps_s, eps_t, cyclic, &g, &voxels, nb);
+    NCA_REFUSE_NULL(g_err, who, out);
+    const int rc = vol_check(who, grid, vol, n_vol, eps_s, eps_t, cyclic, &g, &voxels, nb, &tiles);
     if (rc != NCA_OK) return rc;
-    hipLaunchKernelGGL((voltv_kernel<false>), dim3((unsigned)((int64_t)nb[0] * nb[1] * nb[2])), dim3(TV_BLOCK), 0, (hipStream_t)stream, g, vol, n_vol, voxels,
-                       eps_s, eps_t, cyclic, nb[1], nb[2], (const double*)nullptr, (float*)nullptr, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return vfail(NCA_E_HIP, "nca_vol_tv: %s", hipGetErrorString(e));
-    return NCA_OK;
+    hipLaunchKernelGGL((voltv_kernel<false>), dim3((unsigned)tiles), dim3(TV_BLOCK), 0, (hipStream_t)stream, g, vol, n_vol, voxels, eps_s, eps_t, cyclic, nb[1],
+                       nb[2], (const double*)nullptr, (float*)nullptr, out);
+    return nca_launched(g_err, who);
 }
 
 extern "C" int nca_vol_tv_grad(const NcaGrid* grid, const float* vol, int32_t n_vol, double eps_s, double eps_t, int32_t cyclic, const double* scale,
                                float* g_vol, void* stream) {
+    const char* who = "nca_vol_tv_grad";
     NcaGrid g;
-    int64_t voxels;
+    int64_t voxels, tiles;
     int32_t nb[3];
-    if (!scale) return vfail(NCA_E_INVALID, "nca_vol_tv_grad: scale is NULL");
-    if (!g_vol) return vfail(NCA_E_INVALID, "nca_vol_tv_grad: g_vol is NULL");
-    const int rc = vol_check("nca_vol_tv_grad", grid, vol, n_vol, eps_s, eps_t, cyclic, &g, &voxels, nb);
+    NCA_REFUSE_NULL(g_err, who, scale);
+    NCA_REFUSE_NULL(g_err, who, g_vol);
+    const int rc = vol_check(who, grid, vol, n_vol, eps_s, eps_t, cyclic, &g, &voxels, nb, &tiles);
     if (rc != NCA_OK) return rc;
-    hipLaunchKernelGGL((voltv_kernel<true>), dim3((unsigned)((int64_t)nb[0] * nb[1] * nb[2])), dim3(TV_BLOCK), 0, (hipStream_t)stream, g, vol, n_vol, voxels,
-                       eps_s, eps_t, cyclic, nb[1], nb[2], scale, g_vol, (double*)nullptr);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return vfail(NCA_E_HIP, "nca_vol_tv_grad: %s", hipGetErrorString(e));
-    return NCA_OK;
+    hipLaunchKernelGGL((voltv_kernel<true>), dim3((unsigned)tiles), dim3(TV_BLOCK), 0, (hipStream_t)stream, g, vol, n_vol, voxels, eps_s, eps_t, cyclic, nb[1],
+                       nb[2], scale, g_vol, (double*)nullptr);
+    return nca_launched(g_err, who);
 }

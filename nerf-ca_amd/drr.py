@@ -37,21 +37,14 @@ Bounds = Tuple[Tuple[float, float], ...]
 UNIT_BOUNDS: Bounds = ((-1.0, 1.0),) * 3
 
 
-def grid_desc(shape: Sequence[int], bounds: Bounds) -> "_capi.NcaGrid":
-    """The NcaGrid of a volume of ``shape`` ``(n0, n1, n2)`` whose nodes are ``linspace(lo, hi, n)`` on each axis of ``bounds``:
-    ``lo`` and ``inv = (n - 1) / (hi - lo)``, in f64."""
-    shape = tuple(int(n) for n in shape)
-    if len(shape) != 3 or len(bounds) != 3 or any(len(b) != 2 for b in bounds):
-        raise _capi.NcaError(f"a grid has three axes with (lo, hi) each: got shape {shape} and bounds {bounds!r}")
-    lo = [float(b[0]) for b in bounds]
-    hi = [float(b[1]) for b in bounds]
-    for a in range(3):
-        if shape[a] < 2:
-            raise _capi.NcaError(f"a grid has at least 2 nodes per axis: axis {a} has {shape[a]}")
-        if not (math.isfinite(lo[a]) and math.isfinite(hi[a]) and hi[a] > lo[a]):
-            raise _capi.NcaError(f"bounds of axis {a}: ({lo[a]}, {hi[a]}) is not a finite interval lo < hi")
-    inv = [(shape[a] - 1) / (hi[a] - lo[a]) for a in range(3)]
-    return _capi.NcaGrid(lo=(C.c_double * 3)(*lo), inv=(C.c_double * 3)(*inv), n=(C.c_int32 * 3)(*shape), reserved=0)
+grid_desc = _capi.grid_desc          # the public name; the leaf module has it so that metrics and phantom need not import this one
+
+
+def _check_volumes(volumes, who):
+    """The volume stack ``who`` (an entry point's name) takes: contiguous float32 [n0,n1,n2] or [n_vol,n0,n1,n2], not empty."""
+    if volumes.dtype != torch.float32 or volumes.dim() not in (3, 4) or not volumes.is_contiguous() or volumes.numel() == 0:
+        raise _capi.NcaError(f"{who} takes contiguous float32 volumes [n0,n1,n2] or [n_vol,n0,n1,n2], got {volumes.dtype} "
+                             f"{tuple(volumes.shape)}{'' if volumes.is_contiguous() else ' (not contiguous)'}")
 
 
 def _default_dists(z: torch.Tensor) -> torch.Tensor:
@@ -122,9 +115,7 @@ def _project_rays(volumes, origins, dirs, z, dists, i0, bounds, differentiable):
         _fused._require_cuda(dists, "interval lengths")
     if any(t.device != dev for t in (origins, dirs, z) + (() if dists is None else (dists,))):
         raise _capi.NcaError("project_rays: volumes, rays, depths and interval lengths must live on one device")
-    if volumes.dtype != torch.float32 or volumes.dim() not in (3, 4) or not volumes.is_contiguous() or volumes.numel() == 0:
-        raise _capi.NcaError(f"project_rays takes contiguous float32 volumes [n0,n1,n2] or [n_vol,n0,n1,n2], got {volumes.dtype} "
-                             f"{tuple(volumes.shape)}{'' if volumes.is_contiguous() else ' (not contiguous)'}")
+    _check_volumes(volumes, "project_rays")
     if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape != dirs.shape or origins.shape[0] == 0:
         raise _capi.NcaError(f"project_rays takes ray origins and directions [R,3], got {tuple(origins.shape)} and {tuple(dirs.shape)}")
     if any(t.dtype not in (torch.float32, torch.float64) for t in (origins, dirs)):
@@ -201,9 +192,7 @@ def total_variation(volumes: torch.Tensor, *, bounds: Bounds, eps_space: float =
     With grad mode on and ``volumes.requires_grad`` both results carry a gradient in ``volumes`` (f32, the volumes' shape, one gathered
     kernel launch, the same bits on every run).  In every other case nothing is recorded."""
     _fused._require_cuda(volumes, "volumes")
-    if volumes.dtype != torch.float32 or volumes.dim() not in (3, 4) or not volumes.is_contiguous() or volumes.numel() == 0:
-        raise _capi.NcaError(f"total_variation takes contiguous float32 volumes [n0,n1,n2] or [n_vol,n0,n1,n2], got {volumes.dtype} "
-                             f"{tuple(volumes.shape)}{'' if volumes.is_contiguous() else ' (not contiguous)'}")
+    _check_volumes(volumes, "total_variation")
     eps_space, eps_time = float(eps_space), float(eps_time)
     for eps, what in ((eps_space, "eps_space"), (eps_time, "eps_time")):
         if not (math.isfinite(eps) and eps > 0):

@@ -200,11 +200,6 @@ def compare_sequences(pred: dict, truth: dict, *, data_range: Optional[Union[flo
 MAX_AXIS = 512          # NCA_EDT_MAX_AXIS
 
 
-def _grid_desc(shape, bounds):
-    from . import drr          # (drr imports this module for its structural term)
-    return drr.grid_desc(shape, bounds)
-
-
 def _check_volume(vol, who, what="vol"):
     if not isinstance(vol, torch.Tensor):
         raise _capi.NcaError(f"{who}: {what} is not a tensor")
@@ -231,7 +226,7 @@ def distance_transform(vol: torch.Tensor, bounds, *, threshold: float, inside: b
     if math.isnan(threshold):
         raise _capi.NcaError("distance_transform: threshold = nan is not a number")
     shape = tuple(vol.shape[-3:])
-    desc = _grid_desc(shape, bounds)
+    desc = _capi.grid_desc(shape, bounds)
     x = vol.detach().reshape((-1,) + shape).contiguous()
     n_vol = x.shape[0]
     out = torch.empty_like(x)
@@ -312,7 +307,7 @@ def mask_distances(pred: torch.Tensor, truth: torch.Tensor, bounds, *, threshold
 def nearest_nodes(points, shape, bounds):
     """(index i64 ``[n, 3]``, inside bool ``[n]``) of host points f64 ``[n, 3]``: the node nearest each point, ``floor(g_a + 0.5)`` with
     ``g_a = (x_a - lo_a) inv_a`` of ``drr.grid_desc(shape, bounds)``; ``inside`` is False where an index falls outside the grid."""
-    desc = _grid_desc(shape, bounds)
+    desc = _capi.grid_desc(shape, bounds)
     pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
     lo, inv = np.array(list(desc.lo)), np.array(list(desc.inv))
     idx = np.floor((pts - lo) * inv + 0.5)

@@ -17,7 +17,6 @@ import numpy as np
 import torch
 
 from . import _capi
-from . import drr as _drr
 from . import fused as _fused
 
 SEG_BATCH = 512          # NCA_PHANTOM_SEG_BATCH: the segments staged through LDS at once
@@ -173,7 +172,7 @@ def voxelize(shape: Sequence[int], bounds, *, ellipsoids=None, segments=None, rh
     Refused (``NcaError``), on the host tables before anything is uploaded: a non-finite entry, a negative radius, ``w <= 0``, two tables
     with different phase counts (other than 1), no rows at all, a ``rho_vessel`` that is not finite, an ``edge`` that is not finite and
     positive."""
-    desc = _drr.grid_desc(shape, bounds)
+    desc = _capi.grid_desc(shape, bounds)
     shape = tuple(int(n) for n in shape)
     ell, seg = _table(ellipsoids, 14, "ellipsoids"), _table(segments, 8, "segments")
     if ell is not None and (ell[:, :, 12] <= 0).any():

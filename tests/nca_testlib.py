@@ -3,11 +3,16 @@ the scalar every render-parity test differentiates,
 
     sum(pix * cp) + 50 sum(sigma_s * cs) + 50 sum(sigma_d * cd),
 
-launch counting and the bf16 bounds.  Test modules import from here (and from conftest.py), never from one another.  Every helper
+launch counting, the bf16 bounds, and what the launch-free tests of the view sections (csrc/view/) share: the `capi` / `lib` fixtures, the
+declared-bound-exported check, `refused` and the one list of NcaGrid refusals.  Test modules import from here (and from conftest.py), never from one another.  Every helper
 draws from the generator it is given in a fixed, documented order: the tolerances of the tests were measured on those draws.
 """
 import contextlib
+import ctypes as C
 import dataclasses
+import math
+import os
+import re
 import socket
 
 import pytest
@@ -181,3 +186,78 @@ def count_launches(out, kinds=("fwd", "bwd_dgrad")):
         out.append(n if len(n) > 1 else n[0])
         _capi.timing_enable(False)
         _capi.timing_reset()
+
+
+# ------------------------------------------------------------------------------------------ the view sections' C ABI, without a launch
+E_INVALID, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -4
+FAKE = 0x1000          # a non-NULL pointer a refused call never reads
+
+
+@pytest.fixture(scope="module")
+def capi():
+    from nerfca_amd import _capi
+    return _capi
+
+
+@pytest.fixture(scope="module")
+def lib(capi):
+    return capi.lib()
+
+
+def declared_bound_and_exported(capi, names):
+    """Every name is declared in include/nerfca_hip.h, bound in _capi.SYMBOLS and exported by the library, at ABI 13.  Returns the header's
+    text for the caller's own assertions about it."""
+    from conftest import ROOT
+    header = open(os.path.join(ROOT, "include", "nerfca_hip.h")).read()
+    declared = set(re.findall(r"\b(nca_[a-z0-9_]+)\s*\(", header))
+    raw = C.CDLL(capi.LIB_PATH)
+    for name in names:
+        assert name in declared, name
+        assert name in capi.SYMBOLS, name
+        assert hasattr(raw, name), name
+    assert capi.ABI_VERSION == 13 and capi.lib().nca_abi_version() == 13
+    assert int(re.search(r"#define NCA_ABI_VERSION (\d+)", header).group(1)) == 13
+    return header
+
+
+def refused(section, capi, lib, rc, *words, code=E_INVALID):
+    """The call returned `code`, the section's own message (nca_<section>_last_error) holds every word, and check_<section> raises with it."""
+    msg = getattr(lib, f"nca_{section}_last_error")().decode()
+    assert rc == code, (rc, msg)
+    for w in words:
+        assert w in msg, msg
+    with pytest.raises(capi.NcaError) as e:
+        getattr(capi, f"check_{section}")(rc)
+    assert msg in str(e.value)
+
+
+def grid(capi, n=(5, 3, 4), lo=(-1.0, -1.0, -1.0), inv=(2.0, 1.0, 1.5), reserved=0):
+    return capi.NcaGrid(lo=(C.c_double * 3)(*lo), inv=(C.c_double * 3)(*inv), n=(C.c_int32 * 3)(*n), reserved=reserved)
+
+
+def grid_refusals(section, capi, lib, call):
+    """Every refusal of a bad NcaGrid, for an entry point of `section`: `call(g, count)` makes the call with the descriptor g and `count`
+    volumes or phases (None: the test's own default), everything else valid."""
+    def no(g, *words, count=None):
+        refused(section, capi, lib, call(g, count), *words)
+
+    for a in range(3):
+        for bad in (1, -6):
+            n = [5, 3, 4]
+            n[a] = bad
+            no(grid(capi, n=n), f"n[{a}] = {bad}", "2 nodes")
+        for bad, word in ((math.inf, "inf"), (-math.inf, "-inf"), (math.nan, "nan")):
+            lo, inv = [-1.0] * 3, [2.0, 1.0, 1.5]
+            lo[a] = bad
+            no(grid(capi, lo=lo), f"lo[{a}] = {word}", "finite")
+            inv[a] = bad
+            no(grid(capi, inv=inv), f"inv[{a}] = {word}", "finite")
+        for bad, word in ((0.0, "0"), (-0.25, "-0.25"), (-2.0, "-2")):
+            inv = [2.0, 1.0, 1.5]
+            inv[a] = bad
+            no(grid(capi, inv=inv), f"inv[{a}] = {word}", "positive")
+    for bad in (3, 7):
+        no(grid(capi, reserved=bad), f"reserved = {bad}")
+    big = (1 << 31) - 1
+    no(grid(capi, n=(big, big, big)), "overflow", str(big))
+    no(grid(capi, n=(1 << 20, 1 << 20, 1 << 20)), "overflow", str(1 << 20), count=4)          # 2^60 voxels x 4 x at least 4 bytes

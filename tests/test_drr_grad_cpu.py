@@ -2,10 +2,9 @@
 C-ABI surface, every refusal (with pointers that are never read), the f64 oracle of the GPU tests (tests/drr_adjoint_ref.py) against
 autograd through torch's grid_sample and against the forward oracle's adjoint identity, and the command line's manifest reading."""
 import ctypes as C
+import functools
 import json
-import math
 import os
-import re
 import sys
 
 import numpy as np
@@ -16,50 +15,18 @@ from conftest import ROOT
 
 import drr_adjoint_ref as adj
 import drr_ref as ref
+import nca_testlib as T
+from nca_testlib import FAKE, capi, grid, lib  # noqa: F401
 
 NEW = ("nca_drr_backproject", "nca_drr_set_backproject_runs", "nca_drr_get_backproject_runs")
-E_INVALID = -1
-FAKE = 0x1000          # a non-NULL pointer a refused call never reads
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from nerfca_amd import _capi
-    return _capi
-
-
-@pytest.fixture(scope="module")
-def lib(capi):
-    return capi.lib()
+refused = functools.partial(T.refused, "drr")
 
 
 def test_new_names_are_declared_bound_and_exported(capi):
-    header = open(os.path.join(ROOT, "include", "nerfca_hip.h")).read()
-    declared = set(re.findall(r"\b(nca_[a-z0-9_]+)\s*\(", header))
-    raw = C.CDLL(capi.LIB_PATH)
-    for name in NEW:
-        assert name in declared, name
-        assert name in capi.SYMBOLS, name
-        assert hasattr(raw, name), name
-    assert capi.ABI_VERSION == 13 and capi.lib().nca_abi_version() == 13
-    assert int(re.search(r"#define NCA_ABI_VERSION (\d+)", header).group(1)) == 13
+    header = T.declared_bound_and_exported(capi, NEW)
     assert header.index("int nca_drr_project(") < header.index("int nca_drr_backproject(") < header.index("nca_drr_last_error(void)")
     import nerfca_amd
     assert nerfca_amd.drr.fit_volumes
-
-
-def grid(capi, n=(5, 3, 4), lo=(-1.0, -1.0, -1.0), inv=(2.0, 1.0, 1.5), reserved=0):
-    return capi.NcaGrid(lo=(C.c_double * 3)(*lo), inv=(C.c_double * 3)(*inv), n=(C.c_int32 * 3)(*n), reserved=reserved)
-
-
-def refused(capi, lib, rc, *words):
-    assert rc == E_INVALID, rc
-    msg = lib.nca_drr_last_error().decode()
-    for w in words:
-        assert w in msg, msg
-    with pytest.raises(capi.NcaError) as e:
-        capi.check_drr(rc)
-    assert msg in str(e.value)
 
 
 def test_backproject_refusals(capi, lib):
@@ -76,27 +43,7 @@ def test_backproject_refusals(capi, lib):
     refused(capi, lib, call(R=-7), "R = -7")
     refused(capi, lib, call(S=0), "S = 0")
     refused(capi, lib, call(S=-1), "S = -1")
-    for a in range(3):
-        n = [5, 3, 4]
-        n[a] = 1
-        refused(capi, lib, call(g=grid(capi, n=n)), f"n[{a}] = 1")
-        n[a] = -6
-        refused(capi, lib, call(g=grid(capi, n=n)), f"n[{a}] = -6")
-        for bad, word in ((math.inf, "inf"), (-math.inf, "-inf"), (math.nan, "nan")):
-            lo, inv = [-1.0] * 3, [2.0, 1.0, 1.5]
-            lo[a] = bad
-            refused(capi, lib, call(g=grid(capi, lo=lo)), f"lo[{a}] = {word}", "finite")
-            inv[a] = bad
-            refused(capi, lib, call(g=grid(capi, inv=inv)), f"inv[{a}] = {word}", "finite")
-        inv = [2.0, 1.0, 1.5]
-        inv[a] = 0.0
-        refused(capi, lib, call(g=grid(capi, inv=inv)), f"inv[{a}] = 0", "positive")
-        inv[a] = -0.25
-        refused(capi, lib, call(g=grid(capi, inv=inv)), f"inv[{a}] = -0.25", "positive")
-    refused(capi, lib, call(g=grid(capi, reserved=3)), "reserved = 3")
-    big = (1 << 31) - 1
-    refused(capi, lib, call(g=grid(capi, n=(big, big, big))), "overflow", str(big))
-    refused(capi, lib, call(g=grid(capi, n=(1 << 20, 1 << 20, 1 << 20)), n_vol=2), "overflow", str(1 << 20))          # 2^60 voxels x 2 volumes x 8 bytes
+    T.grid_refusals("drr", capi, lib, lambda g, count: call(g=g, n_vol=count or 1))
     refused(capi, lib, call(R=1 << 62), "R = " + str(1 << 62))
 
 

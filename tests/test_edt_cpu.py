@@ -4,6 +4,7 @@ never read), the workspace query, the numpy oracle of the GPU tests (tests/edt_r
 sampling, the reductions on CPU tensors with the distance maps injected from the oracle, the refusals of the Python layer and the command
 lines."""
 import ctypes as C
+import functools
 import math
 import os
 import re
@@ -17,34 +18,16 @@ import torch
 from conftest import ROOT
 
 import edt_ref as ref
+import nca_testlib as T
+from nca_testlib import E_UNSUPPORTED, E_WORKSPACE, FAKE, capi, lib  # noqa: F401
 
 NEW = ("nca_vol_edt_workspace", "nca_vol_edt", "nca_edt_last_error")
-E_INVALID, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -4
-FAKE = 0x1000          # a non-NULL device pointer a refused call never reads
 MAX_AXIS = 512
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from nerfca_amd import _capi
-    return _capi
-
-
-@pytest.fixture(scope="module")
-def lib(capi):
-    return capi.lib()
+refused = functools.partial(T.refused, "edt")
 
 
 def test_new_names_are_declared_bound_and_exported(capi):
-    header = open(os.path.join(ROOT, "include", "nerfca_hip.h")).read()
-    declared = set(re.findall(r"\b(nca_[a-z0-9_]+)\s*\(", header))
-    raw = C.CDLL(capi.LIB_PATH)
-    for name in NEW:
-        assert name in declared, name
-        assert name in capi.SYMBOLS, name
-        assert hasattr(raw, name), name
-    assert capi.ABI_VERSION == 13 and capi.lib().nca_abi_version() == 13
-    assert int(re.search(r"#define NCA_ABI_VERSION (\d+)", header).group(1)) == 13
+    header = T.declared_bound_and_exported(capi, NEW)
     assert header.index("nca_ssim_last_error(void)") < header.index("size_t nca_vol_edt_workspace(") < header.index("int nca_vol_edt(") < header.index("nca_edt_last_error(void)")
     assert int(re.search(r"NCA_EDT_MAX_AXIS = (\d+)", header).group(1)) == MAX_AXIS >= 512
     assert callable(capi.check_edt)
@@ -54,17 +37,7 @@ def test_new_names_are_declared_bound_and_exported(capi):
 
 
 def grid(capi, n=(4, 5, 6), lo=(0.0, 0.0, 0.0), inv=(1.0, 2.0, 3.0), reserved=0):
-    return capi.NcaGrid(lo=(C.c_double * 3)(*lo), inv=(C.c_double * 3)(*inv), n=(C.c_int32 * 3)(*n), reserved=reserved)
-
-
-def refused(capi, lib, rc, *words, code=E_INVALID):
-    assert rc == code, (rc, lib.nca_edt_last_error().decode())
-    msg = lib.nca_edt_last_error().decode()
-    for w in words:
-        assert w in msg, msg
-    with pytest.raises(capi.NcaError) as e:
-        capi.check_edt(rc)
-    assert msg in str(e.value)
+    return T.grid(capi, n, lo, inv, reserved)
 
 
 def test_refusals(capi, lib):
@@ -82,23 +55,7 @@ def test_refusals(capi, lib):
         refused(capi, lib, call(invert=bad), f"invert = {bad}")
     refused(capi, lib, call(threshold=math.nan), "threshold = nan")
     assert call(threshold=math.inf, work=None) == E_WORKSPACE          # an infinite threshold is a threshold: the call gets as far as the workspace
-    # the grid refusals of nca_drr_project
-    refused(capi, lib, call(reserved=7), "reserved = 7")
-    for a in range(3):
-        n = [4, 5, 6]
-        n[a] = 1
-        refused(capi, lib, call(n=n), f"n[{a}] = 1", "2 nodes")
-        for bad, word in ((math.inf, "inf"), (math.nan, "nan")):
-            lo = [0.0, 0.0, 0.0]
-            lo[a] = bad
-            refused(capi, lib, call(lo=lo), f"lo[{a}] = {word}", "finite")
-            inv = [1.0, 2.0, 3.0]
-            inv[a] = bad
-            refused(capi, lib, call(inv=inv), f"inv[{a}] = {word}", "finite")
-        for bad, word in ((0.0, "0"), (-2.0, "-2")):
-            inv = [1.0, 2.0, 3.0]
-            inv[a] = bad
-            refused(capi, lib, call(inv=inv), f"inv[{a}] = {word}", "positive")
+    T.grid_refusals("edt", capi, lib, lambda g, count: call(g=C.byref(g), n_vol=count or 2))
     big = (1 << 31) - 1
     refused(capi, lib, call(n=(big, big, big), n_vol=big), "overflow", str(big))
     # an axis beyond what a line tile in LDS holds

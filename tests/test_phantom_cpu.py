@@ -2,31 +2,19 @@
 every refusal of the entry points (with pointers that are never read), the f64 oracle of the GPU tests (tests/phantom_ref.py) on its own,
 the host-side generator, and the refusals of the Python layer, which look at the host tables before any device is touched."""
 import ctypes as C
+import functools
 import math
-import os
 import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-
 import phantom_ref as ref
+import nca_testlib as T
+from nca_testlib import FAKE, capi, grid, lib  # noqa: F401
 
 NEW = ("nca_phantom_voxelize", "nca_phantom_set_cull", "nca_phantom_get_cull", "nca_phantom_last_error")
-E_INVALID = -1
-FAKE = 0x1000          # a non-NULL pointer a refused call never reads
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from nerfca_amd import _capi
-    return _capi
-
-
-@pytest.fixture(scope="module")
-def lib(capi):
-    return capi.lib()
+refused = functools.partial(T.refused, "phantom")
 
 
 @pytest.fixture(scope="module")
@@ -36,35 +24,13 @@ def phantom():
 
 
 def test_new_names_are_declared_bound_and_exported(capi, phantom):
-    header = open(os.path.join(ROOT, "include", "nerfca_hip.h")).read()
-    declared = set(re.findall(r"\b(nca_[a-z0-9_]+)\s*\(", header))
-    raw = C.CDLL(capi.LIB_PATH)
-    for name in NEW:
-        assert name in declared, name
-        assert name in capi.SYMBOLS, name
-        assert hasattr(raw, name), name
-    assert capi.ABI_VERSION == 13 and capi.lib().nca_abi_version() == 13
-    assert int(re.search(r"#define NCA_ABI_VERSION (\d+)", header).group(1)) == 13
+    header = T.declared_bound_and_exported(capi, NEW)
     assert header.index("nca_vol_last_error(void)") < header.index("int nca_phantom_voxelize(") < header.index("int nca_phantom_set_cull(") \
         < header.index("nca_phantom_last_error(void)")
     assert int(re.search(r"NCA_PHANTOM_SEG_BATCH = (\d+)", header).group(1)) == phantom.SEG_BATCH
     assert callable(capi.check_phantom)
     import nerfca_amd
     assert nerfca_amd.phantom is phantom and "phantom" in nerfca_amd.__all__
-
-
-def grid(capi, n=(5, 3, 4), lo=(-1.0, -1.0, -1.0), inv=(2.0, 1.0, 1.5), reserved=0):
-    return capi.NcaGrid(lo=(C.c_double * 3)(*lo), inv=(C.c_double * 3)(*inv), n=(C.c_int32 * 3)(*n), reserved=reserved)
-
-
-def refused(capi, lib, rc, *words):
-    assert rc == E_INVALID, rc
-    msg = lib.nca_phantom_last_error().decode()
-    for w in words:
-        assert w in msg, msg
-    with pytest.raises(capi.NcaError) as e:
-        capi.check_phantom(rc)
-    assert msg in str(e.value)
 
 
 def test_refusals(capi, lib):
@@ -86,27 +52,7 @@ def test_refusals(capi, lib):
         refused(capi, lib, call(edge=bad), f"edge = {word}", "positive")
     for bad, word in ((math.inf, "inf"), (-math.inf, "-inf"), (math.nan, "nan")):
         refused(capi, lib, call(rho_v=bad), f"rho_v = {word}", "finite")
-    for a in range(3):
-        n = [5, 3, 4]
-        n[a] = 1
-        refused(capi, lib, call(g=grid(capi, n=n)), f"n[{a}] = 1")
-        n[a] = -6
-        refused(capi, lib, call(g=grid(capi, n=n)), f"n[{a}] = -6")
-        for bad, word in ((math.inf, "inf"), (-math.inf, "-inf"), (math.nan, "nan")):
-            lo, inv = [-1.0] * 3, [2.0, 1.0, 1.5]
-            lo[a] = bad
-            refused(capi, lib, call(g=grid(capi, lo=lo)), f"lo[{a}] = {word}", "finite")
-            inv[a] = bad
-            refused(capi, lib, call(g=grid(capi, inv=inv)), f"inv[{a}] = {word}", "finite")
-        inv = [2.0, 1.0, 1.5]
-        inv[a] = 0.0
-        refused(capi, lib, call(g=grid(capi, inv=inv)), f"inv[{a}] = 0", "positive")
-        inv[a] = -0.25
-        refused(capi, lib, call(g=grid(capi, inv=inv)), f"inv[{a}] = -0.25", "positive")
-    refused(capi, lib, call(g=grid(capi, reserved=3)), "reserved = 3")
-    big = (1 << 31) - 1
-    refused(capi, lib, call(g=grid(capi, n=(big, big, big))), "overflow", str(big))
-    refused(capi, lib, call(g=grid(capi, n=(1 << 20, 1 << 20, 1 << 20)), n_phase=4), "overflow", str(1 << 20))
+    T.grid_refusals("phantom", capi, lib, lambda g, count: call(g=g, n_phase=count or 1))
     # 2^50 voxels fit int64, but make 2^39 tiles of 4 x 8 x 64 nodes: more than the 2^31 - 1 blocks of one launch
     refused(capi, lib, call(g=grid(capi, n=(1 << 20, 1 << 20, 1 << 10))), "tiles", "one launch", str(1 << 39))
     # 2^30 tiles pass alone and are too many with 2 phases: the phase is an outer grid dimension of the same launch

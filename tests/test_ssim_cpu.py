@@ -3,6 +3,7 @@ tools/fit_volumes.py): everything that can be checked without a launch -- the C-
 pointers that are never read), the workspace query, the window, the f64 oracle of the GPU tests (tests/ssim_ref.py) pinned two independent
 ways, the refusals of the Python layer and the command lines."""
 import ctypes as C
+import functools
 import math
 import os
 import re
@@ -16,33 +17,15 @@ import torch
 from conftest import ROOT
 
 import ssim_ref as ref
+import nca_testlib as T
+from nca_testlib import E_WORKSPACE, FAKE, capi, lib  # noqa: F401
 
 NEW = ("nca_ssim", "nca_ssim_grad_workspace", "nca_ssim_grad", "nca_ssim_last_error")
-E_INVALID, E_WORKSPACE = -1, -4
-FAKE = 0x1000          # a non-NULL device pointer a refused call never reads
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from nerfca_amd import _capi
-    return _capi
-
-
-@pytest.fixture(scope="module")
-def lib(capi):
-    return capi.lib()
+refused = functools.partial(T.refused, "ssim")
 
 
 def test_new_names_are_declared_bound_and_exported(capi):
-    header = open(os.path.join(ROOT, "include", "nerfca_hip.h")).read()
-    declared = set(re.findall(r"\b(nca_[a-z0-9_]+)\s*\(", header))
-    raw = C.CDLL(capi.LIB_PATH)
-    for name in NEW:
-        assert name in declared, name
-        assert name in capi.SYMBOLS, name
-        assert hasattr(raw, name), name
-    assert capi.ABI_VERSION == 13 and capi.lib().nca_abi_version() == 13
-    assert int(re.search(r"#define NCA_ABI_VERSION (\d+)", header).group(1)) == 13
+    header = T.declared_bound_and_exported(capi, NEW)
     assert header.index("nca_phantom_last_error(void)") < header.index("int nca_ssim(") < header.index("int nca_ssim_grad(") < header.index("nca_ssim_last_error(void)")
     assert int(re.search(r"NCA_SSIM_MAX_WIN = (\d+)", header).group(1)) == 11
     assert callable(capi.check_ssim)
@@ -52,16 +35,6 @@ def test_new_names_are_declared_bound_and_exported(capi):
 
 def cwin(values):
     return (C.c_double * len(values))(*values)
-
-
-def refused(capi, lib, rc, *words, code=E_INVALID):
-    assert rc == code, (rc, lib.nca_ssim_last_error().decode())
-    msg = lib.nca_ssim_last_error().decode()
-    for w in words:
-        assert w in msg, msg
-    with pytest.raises(capi.NcaError) as e:
-        capi.check_ssim(rc)
-    assert msg in str(e.value)
 
 
 @pytest.mark.parametrize("entry", ["nca_ssim", "nca_ssim_grad"])

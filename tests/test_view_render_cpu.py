@@ -2,6 +2,7 @@
 the C-ABI surface, every refusal (with pointers that are never read), the workspace query, the descriptor packer, the chunk plan and
 the command line of tools/render_views.py."""
 import ctypes as C
+import functools
 import os
 import re
 import sys
@@ -11,20 +12,11 @@ import pytest
 
 from conftest import ROOT
 
+import nca_testlib as T
+from nca_testlib import E_WORKSPACE, FAKE, capi, lib  # noqa: F401
+
 NEW = ("nca_view_rays", "nca_view_points", "nca_view_compose", "nca_image_normalize_workspace", "nca_image_normalize", "nca_view_last_error")
-E_INVALID, E_WORKSPACE = -1, -4
-FAKE = 0x1000          # a non-NULL pointer a refused call never reads
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from nerfca_amd import _capi
-    return _capi
-
-
-@pytest.fixture(scope="module")
-def lib(capi):
-    return capi.lib()
+refused = functools.partial(T.refused, "view")
 
 
 def view(capi, W=4, H=5):
@@ -32,15 +24,7 @@ def view(capi, W=4, H=5):
 
 
 def test_new_names_are_declared_bound_and_exported(capi):
-    header = open(os.path.join(ROOT, "include", "nerfca_hip.h")).read()
-    declared = set(re.findall(r"\b(nca_[a-z0-9_]+)\s*\(", header))
-    raw = C.CDLL(capi.LIB_PATH)
-    for name in NEW:
-        assert name in declared, name
-        assert name in capi.SYMBOLS, name
-        assert hasattr(raw, name), name
-    assert capi.ABI_VERSION == 13 and capi.lib().nca_abi_version() == 13
-    assert int(re.search(r"#define NCA_ABI_VERSION (\d+)", header).group(1)) == 13
+    T.declared_bound_and_exported(capi, NEW)
 
 
 def test_view_descriptor_size_matches_the_header(capi):
@@ -61,71 +45,61 @@ def test_view_descriptor_size_matches_the_header(capi):
     assert [n for n, _ in capi.NcaView._fields_] == ["pose", "W", "H", "d_det", "off_det", "dsd"]
 
 
-def refused(capi, lib, rc, code, *words):
-    assert rc == code, rc
-    msg = lib.nca_view_last_error().decode()
-    for w in words:
-        assert w in msg, msg
-    with pytest.raises(capi.NcaError) as e:
-        capi.check_view(rc)
-    assert msg in str(e.value)
-
-
 def test_view_rays_refusals(capi, lib):
     v = view(capi)          # 4 x 5 = 20 pixels
     rays = lambda vv, p0, n, o=FAKE, d=FAKE: lib.nca_view_rays(C.byref(vv) if vv is not None else None, p0, n, 1, o, d, None)
-    refused(capi, lib, rays(v, 0, 0), E_INVALID, "nca_view_rays", "n = 0")
-    refused(capi, lib, rays(v, 0, -3), E_INVALID, "n = -3")
-    refused(capi, lib, rays(v, -1, 4), E_INVALID, "p0 = -1")
-    refused(capi, lib, rays(v, 17, 4), E_INVALID, "20")
-    refused(capi, lib, rays(v, 21, 1), E_INVALID, "20")
-    refused(capi, lib, rays(v, 1, (1 << 63) - 1), E_INVALID, "20")       # p0 + n does not wrap
-    refused(capi, lib, rays(view(capi, W=0), 0, 1), E_INVALID, "0 x 5")
-    refused(capi, lib, rays(view(capi, H=-2), 0, 1), E_INVALID, "4 x -2")
-    refused(capi, lib, rays(v, 0, 20, o=None), E_INVALID, "NULL")
-    refused(capi, lib, rays(v, 0, 20, d=None), E_INVALID, "NULL")
-    refused(capi, lib, rays(None, 0, 20), E_INVALID, "NULL")
+    refused(capi, lib, rays(v, 0, 0), "nca_view_rays", "n = 0")
+    refused(capi, lib, rays(v, 0, -3), "n = -3")
+    refused(capi, lib, rays(v, -1, 4), "p0 = -1")
+    refused(capi, lib, rays(v, 17, 4), "20")
+    refused(capi, lib, rays(v, 21, 1), "20")
+    refused(capi, lib, rays(v, 1, (1 << 63) - 1), "20")       # p0 + n does not wrap
+    refused(capi, lib, rays(view(capi, W=0), 0, 1), "0 x 5")
+    refused(capi, lib, rays(view(capi, H=-2), 0, 1), "4 x -2")
+    refused(capi, lib, rays(v, 0, 20, o=None), "NULL")
+    refused(capi, lib, rays(v, 0, 20, d=None), "NULL")
+    refused(capi, lib, rays(None, 0, 20), "NULL")
 
 
 def test_view_points_refusals(capi, lib):
     pts = lambda R, S, o=FAKE, d=FAKE, z=FAKE, out=FAKE: lib.nca_view_points(R, S, o, d, z, out, None)
-    refused(capi, lib, pts(0, 8), E_INVALID, "nca_view_points", "not positive")
-    refused(capi, lib, pts(8, 0), E_INVALID, "not positive")
-    refused(capi, lib, pts(-1, 8), E_INVALID, "not positive")
-    refused(capi, lib, pts(8, 8, o=None), E_INVALID, "NULL")
-    refused(capi, lib, pts(8, 8, d=None), E_INVALID, "NULL")
-    refused(capi, lib, pts(8, 8, z=None), E_INVALID, "NULL")
-    refused(capi, lib, pts(8, 8, out=None), E_INVALID, "NULL")
-    refused(capi, lib, pts(1 << 61, 8), E_INVALID, "overflows")
-    refused(capi, lib, pts(1 << 40, 8), E_INVALID, "one launch")
+    refused(capi, lib, pts(0, 8), "nca_view_points", "not positive")
+    refused(capi, lib, pts(8, 0), "not positive")
+    refused(capi, lib, pts(-1, 8), "not positive")
+    refused(capi, lib, pts(8, 8, o=None), "NULL")
+    refused(capi, lib, pts(8, 8, d=None), "NULL")
+    refused(capi, lib, pts(8, 8, z=None), "NULL")
+    refused(capi, lib, pts(8, 8, out=None), "NULL")
+    refused(capi, lib, pts(1 << 61, 8), "overflows")
+    refused(capi, lib, pts(1 << 40, 8), "one launch")
 
 
 def test_view_compose_refusals(capi, lib):
     comp = lambda n, s=FAKE, p=FAKE, ps=FAKE, pd=FAKE: lib.nca_view_compose(n, 2.0, s, FAKE, 1, p, ps, pd, None)
-    refused(capi, lib, comp(0), E_INVALID, "nca_view_compose", "n = 0")
-    refused(capi, lib, comp(-5), E_INVALID, "n = -5")
-    refused(capi, lib, comp(4, s=None), E_INVALID, "pix_s is NULL")
-    refused(capi, lib, comp(4, p=None), E_INVALID, "NULL")
-    refused(capi, lib, comp(4, ps=None), E_INVALID, "NULL")
-    refused(capi, lib, comp(4, pd=None), E_INVALID, "NULL")
+    refused(capi, lib, comp(0), "nca_view_compose", "n = 0")
+    refused(capi, lib, comp(-5), "n = -5")
+    refused(capi, lib, comp(4, s=None), "pix_s is NULL")
+    refused(capi, lib, comp(4, p=None), "NULL")
+    refused(capi, lib, comp(4, ps=None), "NULL")
+    refused(capi, lib, comp(4, pd=None), "NULL")
 
 
 def test_image_normalize_refusals_and_workspace(capi, lib):
     ws = lib.nca_image_normalize_workspace
     norm = lambda k, n, img=FAKE, mm=FAKE, work=FAKE, wb=1 << 30: lib.nca_image_normalize(k, n, img, None, mm, work, wb, None)
-    refused(capi, lib, ws(0), E_INVALID, "nca_image_normalize_workspace", "n = 0")
-    refused(capi, lib, ws(-7), E_INVALID, "n = -7")
+    refused(capi, lib, ws(0), "nca_image_normalize_workspace", "n = 0")
+    refused(capi, lib, ws(-7), "n = -7")
     sizes = [ws(n) for n in (1, 2, 255, 256, 257, 2048, 2049, 70001, 1 << 20, 1 << 24, 1 << 31, 1 << 40)]
     assert all(b > 0 and b % 256 == 0 for b in sizes), sizes
     assert sizes == sorted(sizes) and sizes[0] < sizes[-1], sizes
-    refused(capi, lib, norm(0, 16), E_INVALID, "nca_image_normalize", "n_img = 0")
-    refused(capi, lib, norm(-1, 16), E_INVALID, "n_img = -1")
-    refused(capi, lib, norm(2, 0), E_INVALID, "n = 0")
-    refused(capi, lib, norm(2, 16, img=None), E_INVALID, "img is NULL")
-    refused(capi, lib, norm(2, 16, mm=None), E_INVALID, "minmax is NULL")
-    refused(capi, lib, norm(3, 70001, wb=3 * ws(70001) - 1), E_WORKSPACE, str(3 * ws(70001)))
-    refused(capi, lib, norm(3, 70001, wb=ws(70001)), E_WORKSPACE, "workspace")          # one image's worth for three images
-    refused(capi, lib, norm(1, 16, work=None), E_WORKSPACE, "workspace")
+    refused(capi, lib, norm(0, 16), "nca_image_normalize", "n_img = 0")
+    refused(capi, lib, norm(-1, 16), "n_img = -1")
+    refused(capi, lib, norm(2, 0), "n = 0")
+    refused(capi, lib, norm(2, 16, img=None), "img is NULL")
+    refused(capi, lib, norm(2, 16, mm=None), "minmax is NULL")
+    refused(capi, lib, norm(3, 70001, wb=3 * ws(70001) - 1), str(3 * ws(70001)), code=E_WORKSPACE)
+    refused(capi, lib, norm(3, 70001, wb=ws(70001)), "workspace", code=E_WORKSPACE)          # one image's worth for three images
+    refused(capi, lib, norm(1, 16, work=None), "workspace", code=E_WORKSPACE)
 
 
 def test_pack_view_reproduces_the_f32_pose():

@@ -3,6 +3,7 @@ tools/fit_volumes.py): everything that can be checked without a launch -- the C-
 pointers that are never read), the f64 oracle of the GPU tests (tests/voltv_ref.py) against torch autograd in f64, the refusals of the
 Python layer and the command line."""
 import ctypes as C
+import functools
 import math
 import os
 import re
@@ -16,51 +17,19 @@ from conftest import ROOT
 
 import drr_ref
 import voltv_ref as ref
+import nca_testlib as T
+from nca_testlib import FAKE, capi, grid, lib  # noqa: F401
 
 NEW = ("nca_vol_tv", "nca_vol_tv_grad", "nca_vol_last_error")
-E_INVALID = -1
-FAKE = 0x1000          # a non-NULL pointer a refused call never reads
-
-
-@pytest.fixture(scope="module")
-def capi():
-    from nerfca_amd import _capi
-    return _capi
-
-
-@pytest.fixture(scope="module")
-def lib(capi):
-    return capi.lib()
+refused = functools.partial(T.refused, "vol")
 
 
 def test_new_names_are_declared_bound_and_exported(capi):
-    header = open(os.path.join(ROOT, "include", "nerfca_hip.h")).read()
-    declared = set(re.findall(r"\b(nca_[a-z0-9_]+)\s*\(", header))
-    raw = C.CDLL(capi.LIB_PATH)
-    for name in NEW:
-        assert name in declared, name
-        assert name in capi.SYMBOLS, name
-        assert hasattr(raw, name), name
-    assert capi.ABI_VERSION == 13 and capi.lib().nca_abi_version() == 13
-    assert int(re.search(r"#define NCA_ABI_VERSION (\d+)", header).group(1)) == 13
+    header = T.declared_bound_and_exported(capi, NEW)
     assert header.index("nca_drr_last_error(void)") < header.index("int nca_vol_tv(") < header.index("int nca_vol_tv_grad(") < header.index("nca_vol_last_error(void)")
     assert callable(capi.check_vol)
     import nerfca_amd
     assert nerfca_amd.drr.total_variation
-
-
-def grid(capi, n=(5, 3, 4), lo=(-1.0, -1.0, -1.0), inv=(2.0, 1.0, 1.5), reserved=0):
-    return capi.NcaGrid(lo=(C.c_double * 3)(*lo), inv=(C.c_double * 3)(*inv), n=(C.c_int32 * 3)(*n), reserved=reserved)
-
-
-def refused(capi, lib, rc, *words):
-    assert rc == E_INVALID, rc
-    msg = lib.nca_vol_last_error().decode()
-    for w in words:
-        assert w in msg, msg
-    with pytest.raises(capi.NcaError) as e:
-        capi.check_vol(rc)
-    assert msg in str(e.value)
 
 
 @pytest.mark.parametrize("entry", ["nca_vol_tv", "nca_vol_tv_grad"])
@@ -82,27 +51,7 @@ def test_refusals(capi, lib, entry):
     for name in ("eps_s", "eps_t"):
         for bad, word in ((0.0, "0"), (-1e-3, "-0.001"), (math.inf, "inf"), (-math.inf, "-inf"), (math.nan, "nan")):
             refused(capi, lib, call(**{name: bad}), f"{name} = {word}", "positive")
-    for a in range(3):
-        n = [5, 3, 4]
-        n[a] = 1
-        refused(capi, lib, call(g=grid(capi, n=n)), f"n[{a}] = 1")
-        n[a] = -6
-        refused(capi, lib, call(g=grid(capi, n=n)), f"n[{a}] = -6")
-        for bad, word in ((math.inf, "inf"), (-math.inf, "-inf"), (math.nan, "nan")):
-            lo, inv = [-1.0] * 3, [2.0, 1.0, 1.5]
-            lo[a] = bad
-            refused(capi, lib, call(g=grid(capi, lo=lo)), f"lo[{a}] = {word}", "finite")
-            inv[a] = bad
-            refused(capi, lib, call(g=grid(capi, inv=inv)), f"inv[{a}] = {word}", "finite")
-        inv = [2.0, 1.0, 1.5]
-        inv[a] = 0.0
-        refused(capi, lib, call(g=grid(capi, inv=inv)), f"inv[{a}] = 0", "positive")
-        inv[a] = -0.25
-        refused(capi, lib, call(g=grid(capi, inv=inv)), f"inv[{a}] = -0.25", "positive")
-    refused(capi, lib, call(g=grid(capi, reserved=3)), "reserved = 3")
-    big = (1 << 31) - 1
-    refused(capi, lib, call(g=grid(capi, n=(big, big, big))), "overflow", str(big))
-    refused(capi, lib, call(g=grid(capi, n=(1 << 20, 1 << 20, 1 << 20)), n_vol=4), "overflow", str(1 << 20))          # 2^60 voxels x 4 volumes x 4 bytes
+    T.grid_refusals("vol", capi, lib, lambda g, count: call(g=g, n_vol=count or 1))
     # 2^50 voxels fit int64 with room to spare, but make 2^39 tiles of 4 x 8 x 64 nodes: more than the 2^31 - 1 blocks of one launch
     refused(capi, lib, call(g=grid(capi, n=(1 << 20, 1 << 20, 1 << 10))), "tiles", "one launch", str(1 << 39))
 
