@@ -792,6 +792,63 @@ int nca_vol_edt(const NcaGrid* grid, const float* vol, int32_t n_vol, double thr
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_edt_last_error(void);
 
+/* ---- filt: Gaussian smoothing and the city-block distance of voxel stacks (ccta.gaussian_filter / cityblock_distance / binary_dilation /
+ *      binary_erosion / mask_border / vessel_contrast / prepare_ccta, surface=True of metrics.mask_distances) ---------------------------------
+ * The two filters the CCTA pipeline of the reference takes from scipy.ndimage: a separable symmetric filter with the `reflect` boundary,
+ * and the distance in nodes along the axes (L1) to the nearest node above (or, inverted, not above) a threshold, from which every 6-connected
+ * dilation, erosion and mask border follows by a comparison.  Purely additive to ABI 13.  Like the view, drr, vol, phantom, ssim and edt
+ * sections, these entry points keep their OWN per-thread message (the accessor below); a refused call launches nothing and reads no device
+ * pointer; a launch failure is reported once.  vol is f32 [n_vol][n0][n1][n2] contiguous on the device, on one NcaGrid (`grid` is a host pointer; lo
+ * and inv are validated but unused: both filters count in nodes).  Every volume is filtered on its own: its result does not depend on n_vol or on its
+ * neighbours in the stack.
+ *
+ * SMOOTHING.  radius: HOST int32 [3], 0 <= radius[a] <= NCA_SMOOTH_MAX_RADIUS.  weights: HOST f64, the half-weights of axis 0, then of axis
+ * 1, then of axis 2, radius[a] + 1 each: w[0] is the centre, w[k] the weight of both nodes k away.  Any finite non-negative numbers (the
+ * library never calls exp; ccta.gaussian_weights makes scipy's Gaussian and hands its bits over).  Every operation below is ONE rounded f64
+ * operation in the order written (the kernels spell each one out: nothing leans on a contraction flag).
+ *     x = (double)vol, exact.  The axes are filtered in the order 0, 1, 2, each on the result of the one before, with that axis's r and w:
+ *     y[i] = x[i] w[0];   then for k = r, r - 1, .., 1 (the outermost pair first):   y[i] = y[i] + (x[R(i - k)] + x[R(i + k)]) w[k];
+ *     R(j) = m if m < n, else 2 n - 1 - m, with m = j mod 2 n in 0 .. 2 n - 1 (scipy's `reflect`: d c b a | a b c d | d c b a; the map has
+ *     period 2 n, so r may exceed the axis).   out = (float)(the result of axis 2): the one rounding to f32.
+ * An axis with r = 0 and w[0] = 1 is x 1.0: unchanged.  In this order the result has the bits of
+ * scipy.ndimage.gaussian_filter(x.astype(f64), sigma, radius=r, mode="reflect").astype(f32) (tests/test_filt_cpu.py); with the pairs summed
+ * innermost first it is 1 ulp off.  Three launches (axis 0: f32 -> f64, axis 1: f64 -> f64, axis 2: f64 -> f32), each staging a tile of
+ * lines with its reflected halo in LDS; the two f64 intermediates are the workspace: 16 bytes per node, rounded up to a multiple of 256.  The
+ * 40 bytes per node the three launches read and write are what the filter moves.  The tiling sets no limit on an axis.  Every node of every
+ * stage is written once by one thread: no atomics, the same bits on every run.  out may NOT alias vol (out == vol is refused; an overlap
+ * is not detected).
+ * NCA_E_INVALID (the message names the value): a NULL grid, vol, radius, weights or out; out == vol; n_vol <= 0; the grid refusals of
+ * nca_drr_project; a negative radius; a weight that is not finite or is negative; more than 2^24 workgroups in one of the three launches.
+ * NCA_E_UNSUPPORTED: a radius above NCA_SMOOTH_MAX_RADIUS.  NCA_E_WORKSPACE: work is NULL or work_bytes is below the query's answer.  The
+ * query returns 0 for a grid or n_vol the entry point refuses. */
+enum { NCA_SMOOTH_MAX_RADIUS = 32 };
+size_t nca_vol_smooth_workspace(const NcaGrid* grid, int32_t n_vol);
+int nca_vol_smooth(const NcaGrid* grid, const float* vol, int32_t n_vol, const int32_t radius[3], const double* weights, float* out, void* work,
+                   size_t work_bytes, void* stream);
+
+/* CITY-BLOCK DISTANCE.  Node j of volume v is a FEATURE iff ((double)vol[v][j] > threshold) != (invert != 0), the rule of nca_vol_edt: a
+ * NaN value and a value equal to the threshold are features only under invert.
+ *     out[v][i] = min over the features j of volume v of (|i_0 - j_0| + |i_1 - j_1| + |i_2 - j_2|),   an int32 count of nodes;
+ *     with border = 1 the nodes just outside the grid are features too: the minimum also runs over min(i_a + 1, n_a - i_a), a = 0, 1, 2.
+ * A volume without a feature and without a border gives 0x7fffffff at every node; a feature node gets 0.  Exact in integers; the sentinel is
+ * never added to.  Formed separably: g = the distance to the nearest feature of the row (axis 2), b = min_j1 (|i_1 - j_1| + g),
+ * out = min_j0 (|i_0 - j_0| + b), each stage with its own axis's border term.  Every node of every stage is written once by one thread: no
+ * atomics, the same bits on every run.  With M = (vol > threshold), in scipy.ndimage's terms (6-connected structure, border_value 0):
+ *     out <= n             (invert 0, border 0)  is binary_dilation(M, iterations=n);       out itself is distance_transform_cdt(~M, "taxicab");
+ *     out > n              (invert 1, border 1)  is binary_erosion(M, iterations=n);         M and out == 1 is M ^ binary_erosion(M), the border.
+ * The workspace holds g and b as int32 for every node: 8 bytes per node, rounded up to a multiple of 256.  The query returns it, and 0 for
+ * arguments the entry point refuses.
+ * NCA_E_INVALID (the message names the value): a NULL grid, vol or out; n_vol <= 0; invert or border not 0 / 1; a threshold that is NaN; the
+ * grid refusals of nca_drr_project; more than 2^24 workgroups in one of the three launches (rows / 4, or tiles of 16 lines).
+ * NCA_E_UNSUPPORTED: an axis longer than NCA_EDT_MAX_AXIS (a line tile of 16 x n_a int32 values is staged in LDS, and the row pass keeps
+ * NCA_EDT_MAX_AXIS / 64 masks per row).  NCA_E_WORKSPACE: work is NULL or work_bytes is below the query's answer. */
+size_t nca_vol_cityblock_workspace(const NcaGrid* grid, int32_t n_vol);
+int nca_vol_cityblock(const NcaGrid* grid, const float* vol, int32_t n_vol, double threshold, int32_t invert, int32_t border, int32_t* out, void* work,
+                      size_t work_bytes, void* stream);
+
+/* The message of the calling thread's last failed call of this section. */
+const char* nca_filt_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

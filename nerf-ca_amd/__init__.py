@@ -8,5 +8,6 @@ from .fused import render_rays, eval_points, set_precision  # noqa: F401
 from . import drr  # noqa: F401
 from . import phantom  # noqa: F401
 from . import metrics  # noqa: F401
+from . import ccta  # noqa: F401
 
-__all__ = ["render_rays", "eval_points", "set_precision", "drr", "phantom", "metrics"]
+__all__ = ["render_rays", "eval_points", "set_precision", "drr", "phantom", "metrics", "ccta"]

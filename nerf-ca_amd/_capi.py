@@ -235,6 +235,11 @@ SYMBOLS = {
     "nca_vol_edt_workspace": (C.c_size_t, [C.POINTER(NcaGrid), _I32]),
     "nca_vol_edt": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, _I32, _P, _P, C.c_size_t, _P]),
     "nca_edt_last_error": (C.c_char_p, []),
+    "nca_vol_smooth_workspace": (C.c_size_t, [C.POINTER(NcaGrid), _I32]),
+    "nca_vol_smooth": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.POINTER(C.c_int32), C.POINTER(C.c_double), _P, _P, C.c_size_t, _P]),
+    "nca_vol_cityblock_workspace": (C.c_size_t, [C.POINTER(NcaGrid), _I32]),
+    "nca_vol_cityblock": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, _I32, _I32, _P, _P, C.c_size_t, _P]),
+    "nca_filt_last_error": (C.c_char_p, []),
 }
 
 
@@ -279,6 +284,7 @@ check_vol = _section_check("nca_vol_last_error", "volume-prior entry points (nca
 check_phantom = _section_check("nca_phantom_last_error", "phantom entry points (nca_phantom_*)")
 check_ssim = _section_check("nca_ssim_last_error", "image-similarity entry points (nca_ssim*)")
 check_edt = _section_check("nca_edt_last_error", "distance-transform entry points (nca_vol_edt*)")
+check_filt = _section_check("nca_filt_last_error", "filter entry points (nca_vol_smooth*, nca_vol_cityblock*)")
 
 
 def ptr(t) -> Optional[int]:

@@ -1,0 +1,252 @@
+"""From a CT and a vessel segmentation to the two volumes that get projected, on the device: the preprocessing of the reference's
+preprocess/preprocess_ccta.py:54-130 without scipy.ndimage and without a host copy (csrc/view/nca_filt.hip).
+
+``gaussian_filter`` is ``scipy.ndimage.gaussian_filter`` with the ``reflect`` boundary (``nca_vol_smooth``: separable, f64 inside, one
+rounding to f32).  ``cityblock_distance`` counts nodes along the axes to the nearest node above (or not above) a threshold
+(``nca_vol_cityblock``); ``binary_dilation``, ``binary_erosion`` and ``mask_border`` are one such call and a comparison, for the
+6-connected structure and any number of iterations.  Both definitions, operation by operation, are in include/nerfca_hip.h ("filt").
+``vessel_contrast`` and ``prepare_ccta`` chain them with ``metrics.distance_transform`` into the reference's pipeline: a static attenuation
+volume without the vessels and a dynamic vessel-contrast volume, in the shapes ``drr.project_sequence``, ``drr.volume_teacher`` and
+``drr.fit_volumes`` take.  There is no torch implementation behind the two kernels: without the library these functions raise.
+
+Not here: the cubic-spline ``zoom`` to unit spacing (volumes come in on the grid of ``bounds``; the distance transform honours anisotropic
+spacings), file readers, other boundary modes, other structuring elements, gradients.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _capi
+from . import fused as _fused
+from . import metrics as _metrics
+
+MAX_RADIUS = 32          # NCA_SMOOTH_MAX_RADIUS
+MAX_AXIS = 512           # NCA_EDT_MAX_AXIS: the city-block transform stages whole lines
+
+MU_WATER = 0.1494 * 2.5e-2
+MU_AIR = 0.0430 * 2.5e-2
+
+
+def gaussian_weights(sigma: float, radius: Optional[int] = None, truncate: float = 4.0) -> np.ndarray:
+    """The half-weights ``w[0 .. r]`` (``w[0]`` the centre) of scipy's Gaussian kernel, numpy f64: ``phi = exp(-0.5 / sigma^2 x^2)`` at
+    ``x = -r .. r`` divided by its sum, with ``r = radius`` or ``int(truncate sigma + 0.5)``.  The right half is mirrored from the left, so the
+    kernel is symmetric bit for bit.  ``sigma <= 1e-15`` gives ``[1.0]``: scipy leaves such an axis as it is."""
+    sigma, truncate = float(sigma), float(truncate)
+    if not (math.isfinite(sigma) and sigma >= 0.0):
+        raise _capi.NcaError(f"gaussian_weights: sigma = {sigma} is not finite and non-negative")
+    if not sigma > 1e-15:
+        return np.ones(1, dtype=np.float64)
+    if radius is None:
+        if not (math.isfinite(truncate) and truncate >= 0.0):
+            raise _capi.NcaError(f"gaussian_weights: truncate = {truncate} is not finite and non-negative")
+        r = int(truncate * sigma + 0.5)
+    else:
+        r = int(radius)
+        if r != radius or r < 0:
+            raise _capi.NcaError(f"gaussian_weights: radius = {radius} is not a non-negative whole number")
+    if r > MAX_RADIUS:
+        raise _capi.NcaError(f"gaussian_weights: radius = {r} is larger than {MAX_RADIUS} (sigma = {sigma}, truncate = {truncate})")
+    x = np.arange(-r, r + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return np.ascontiguousarray(phi[:r + 1][::-1])          # x = 0, -1, .., -r
+
+
+def _per_axis(value, name, who):
+    if isinstance(value, (tuple, list, np.ndarray)):
+        if len(value) != 3:
+            raise _capi.NcaError(f"{who}: {name} is a scalar or one value per axis, got {value!r}")
+        return list(value)
+    return [value] * 3
+
+
+@torch.no_grad()
+def gaussian_filter(vol: torch.Tensor, sigma, *, radius=None, truncate: float = 4.0) -> torch.Tensor:
+    """``scipy.ndimage.gaussian_filter(vol.astype(f64), sigma, radius=radius, truncate=truncate, mode="reflect").astype(f32)`` of every
+    volume of the f32 stack ``vol`` ``[..., n0, n1, n2]`` on the device, bit for bit: an f32 tensor of the same shape.  ``sigma`` and
+    ``radius`` are a scalar or one value per axis, in nodes; an axis with ``sigma <= 1e-15`` is left as it is.  A radius above 32 is refused.
+
+    One ``nca_vol_smooth`` (three launches, f64 intermediates; the summation order is part of the definition in include/nerfca_hip.h,
+    "filt"): the same bits on every run.  Not differentiable: it runs under ``no_grad`` and the result is detached."""
+    _metrics._check_volume(vol, "gaussian_filter")
+    sig = _per_axis(sigma, "sigma", "gaussian_filter")
+    rad = _per_axis(radius, "radius", "gaussian_filter")
+    halves = [gaussian_weights(s, r, truncate) for s, r in zip(sig, rad)]
+    shape = tuple(vol.shape[-3:])
+    desc = _capi.grid_desc(shape, tuple((0.0, float(n - 1)) for n in shape))
+    x = vol.detach().reshape((-1,) + shape).contiguous()
+    n_vol = x.shape[0]
+    out = torch.empty_like(x)
+    c_radius = (C.c_int32 * 3)(*[len(h) - 1 for h in halves])
+    flat = np.concatenate(halves)
+    c_weights = (C.c_double * flat.size)(*flat.tolist())
+    lib = _capi.lib()
+    nbytes = int(lib.nca_vol_smooth_workspace(C.byref(desc), n_vol))
+    work = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _capi.check_filt(lib.nca_vol_smooth(C.byref(desc), _capi.ptr(x), n_vol, c_radius, c_weights, _capi.ptr(out), _capi.ptr(work), nbytes, _fused._stream()))
+    return out.reshape(vol.shape)
+
+
+@torch.no_grad()
+def cityblock_distance(vol: torch.Tensor, *, threshold: float, inside: bool = False, border: bool = False) -> torch.Tensor:
+    """The city-block (L1) distance in nodes, ``|d0| + |d1| + |d2|``, from every node of the f32 stack ``vol`` ``[..., n0, n1, n2]`` on the
+    device to the nearest node with ``vol > threshold`` (``inside=False``; 0 on the mask) or to the nearest node that is NOT ``> threshold``
+    (``inside=True``; 0 off the mask): an int32 tensor of the same shape.  ``border=True`` counts the nodes just outside the grid as such
+    nodes too.  A NaN value is not ``> threshold``.  A volume with no such node (and no border) is ``0x7fffffff`` everywhere; every volume is
+    transformed on its own.  ``inside=False`` is ``scipy.ndimage.distance_transform_cdt(~(vol > threshold), metric="taxicab")``.
+
+    One ``nca_vol_cityblock`` (three launches, exact in integers): the same bits on every run.  An axis longer than 512 nodes is refused."""
+    _metrics._check_volume(vol, "cityblock_distance")
+    threshold = float(threshold)
+    if math.isnan(threshold):
+        raise _capi.NcaError("cityblock_distance: threshold = nan is not a number")
+    shape = tuple(vol.shape[-3:])
+    desc = _capi.grid_desc(shape, tuple((0.0, float(n - 1)) for n in shape))
+    x = vol.detach().reshape((-1,) + shape).contiguous()
+    n_vol = x.shape[0]
+    out = torch.empty(x.shape, dtype=torch.int32, device=x.device)
+    lib = _capi.lib()
+    nbytes = int(lib.nca_vol_cityblock_workspace(C.byref(desc), n_vol))
+    work = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _capi.check_filt(lib.nca_vol_cityblock(C.byref(desc), _capi.ptr(x), n_vol, threshold, 1 if inside else 0, 1 if border else 0, _capi.ptr(out),
+                                               _capi.ptr(work), nbytes, _fused._stream()))
+    return out.reshape(vol.shape)
+
+
+def _mask_input(vol, who):
+    """f32 on the device from an f32 stack or a bool mask (a mask becomes 0 / 1, which any threshold in [0, 1) separates)."""
+    if isinstance(vol, torch.Tensor) and vol.dtype == torch.bool:
+        _fused._require_cuda(vol, "vol")
+        vol = vol.to(torch.float32)
+    _metrics._check_volume(vol, who)
+    return vol
+
+
+def _iterations(iterations, who):
+    n = int(iterations)
+    if n != iterations or n < 1:
+        raise _capi.NcaError(f"{who}: iterations = {iterations} is not a whole number >= 1 (the repeat-until-stable mode of scipy is not offered)")
+    return n
+
+
+@torch.no_grad()
+def binary_dilation(vol: torch.Tensor, iterations: int = 1, *, threshold: float = 0.0) -> torch.Tensor:
+    """``scipy.ndimage.binary_dilation(vol > threshold, iterations=iterations)`` with the default 6-connected structure, per volume of
+    the stack ``[..., n0, n1, n2]`` (f32, or a bool mask) on the device: a bool tensor of the same shape.  One ``cityblock_distance`` and
+    a comparison, ``distance <= iterations``, whatever the number of iterations."""
+    n = _iterations(iterations, "binary_dilation")
+    return cityblock_distance(_mask_input(vol, "binary_dilation"), threshold=threshold) <= n
+
+
+@torch.no_grad()
+def binary_erosion(vol: torch.Tensor, iterations: int = 1, *, threshold: float = 0.0) -> torch.Tensor:
+    """``scipy.ndimage.binary_erosion(vol > threshold, iterations=iterations)`` (6-connected, ``border_value = 0``: the mask is eroded from
+    the faces of the grid too), as a bool tensor: the distance to the nearest node off the mask or outside the grid is ``> iterations``."""
+    n = _iterations(iterations, "binary_erosion")
+    return cityblock_distance(_mask_input(vol, "binary_erosion"), threshold=threshold, inside=True, border=True) > n
+
+
+@torch.no_grad()
+def mask_border(vol: torch.Tensor, *, threshold: float) -> torch.Tensor:
+    """The nodes of ``M = vol > threshold`` that one erosion removes, ``M & ~binary_erosion(M)``, as a bool tensor: the surface of a mask
+    as MedPy's surface distances take it (connectivity 1).  A node of M on a face of the grid is a border node."""
+    return cityblock_distance(_mask_input(vol, "mask_border"), threshold=threshold, inside=True, border=True) == 1
+
+
+def hounsfield_to_attenuation(vol: torch.Tensor, mu_water: float = MU_WATER, mu_air: float = MU_AIR) -> torch.Tensor:
+    """``vol / 1000 * (mu_water - mu_air) + mu_water`` (preprocess_ccta.py:7-12), formed in f64 and rounded to f32 once.  Plain torch, on
+    whatever device ``vol`` lives on."""
+    if not isinstance(vol, torch.Tensor):
+        raise _capi.NcaError("hounsfield_to_attenuation: vol is not a tensor")
+    return _attenuation64(vol, mu_water, mu_air).to(torch.float32)
+
+
+def _attenuation64(vol, mu_water=MU_WATER, mu_air=MU_AIR):
+    return vol.double() / 1000 * (float(mu_water) - float(mu_air)) + float(mu_water)
+
+
+def _interp(x, xp, fp):
+    """``np.interp(x, xp, fp)`` of an f64 tensor: clamped at both ends, ``slope (x - xp[j]) + fp[j]`` in between."""
+    xp_t = torch.tensor(xp, dtype=torch.float64, device=x.device)
+    fp_t = torch.tensor(fp, dtype=torch.float64, device=x.device)
+    j = (torch.bucketize(x, xp_t, right=True) - 1).clamp(0, len(xp) - 2)
+    slope = (fp_t[1:] - fp_t[:-1]) / (xp_t[1:] - xp_t[:-1])
+    y = slope[j] * (x - xp_t[j]) + fp_t[j]
+    y = torch.where(x >= xp_t[-1], fp_t[-1], y)
+    return torch.where(x <= xp_t[0], fp_t[0], y)
+
+
+@torch.no_grad()
+def vessel_contrast(mask: torch.Tensor, bounds, *, grow: int = 3, shrink: int = 1, sigma=1.0, radius=2, xp: Sequence[float] = (0, 1, 2, 4, 5),
+                    fp: Sequence[float] = (0, 0.2, 0.5, 0.75, 1), contrast: float = 0.05) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The vessel-contrast volume of preprocess_ccta.py:88-120 from a vessel segmentation ``mask`` ``[..., n0, n1, n2]`` (f32, or bool;
+    a node belongs to it when ``> 0``) on the device: ``(contrast volume f32, closed mask bool)``.
+
+    1. ``M = binary_erosion(binary_dilation(mask > 0, grow), shrink)``: the closed mask;
+    2. ``metrics.distance_transform(M, bounds, threshold=0.5, inside=True)``: the depth of every node inside M, in the world units of
+       ``bounds`` (the reference has resampled to unit spacing before this step);
+    3. ``gaussian_filter(sigma, radius=radius)``;
+    4. ``np.interp`` through ``(xp, fp * contrast)``, clamped at both ends, in f64 (``bucketize`` and a lerp), rounded to f32;
+    5. 0 outside M.
+    Steps 2 and 3 hand over f32 volumes where the reference keeps f64: the result is within
+    ``s 2^-24 d_max + 2^-24 max(fp) contrast`` of it (s the largest slope of the transfer function, d_max the largest depth)."""
+    who = "vessel_contrast"
+    m = _mask_input(mask, who)
+    xp, fp, contrast = [float(v) for v in xp], [float(v) for v in fp], float(contrast)
+    if len(xp) != len(fp) or len(xp) < 2:
+        raise _capi.NcaError(f"{who}: xp and fp are two lists of one length >= 2, got {len(xp)} and {len(fp)}")
+    if any(not (math.isfinite(a) and math.isfinite(b)) for a, b in zip(xp, fp)) or any(not a < b for a, b in zip(xp, xp[1:])):
+        raise _capi.NcaError(f"{who}: xp = {xp} is not finite and strictly increasing")
+    if not math.isfinite(contrast):
+        raise _capi.NcaError(f"{who}: contrast = {contrast} is not finite")
+    closed = binary_erosion(binary_dilation(m, grow), shrink)
+    depth = _metrics.distance_transform(closed.to(torch.float32), bounds, threshold=0.5, inside=True)
+    smooth = gaussian_filter(depth, sigma, radius=radius)
+    value = _interp(smooth.double(), xp, [v * contrast for v in fp]).to(torch.float32)
+    return torch.where(closed, value, torch.zeros((), dtype=torch.float32, device=value.device)), closed
+
+
+@torch.no_grad()
+def prepare_ccta(raw_hu: torch.Tensor, vessel_mask: torch.Tensor, bounds, *, labels: Optional[torch.Tensor] = None, aorta_label: Optional[int] = None,
+                 heart_label: Optional[int] = None, **vessel_kw) -> dict:
+    """A CT in Hounsfield units ``raw_hu`` and a vessel segmentation ``vessel_mask``, both ``[P, n0, n1, n2]`` (or one volume
+    ``[n0, n1, n2]``) on the device and on the grid of ``bounds``, to the pair of volumes that gets projected (preprocess_ccta.py:54-130
+    without the resampling): ``{"static", "dynamic", "mask", "bounds"}``.
+
+    1. ``hounsfield_to_attenuation(raw_hu)``;
+    2. with ``labels`` (a segmentation of the same shape, any integer or float dtype): the nodes with ``labels == aorta_label`` get the mean
+       (f64) of the nodes with ``labels == heart_label`` of the same volume -- NaN if that volume has no heart node, as numpy's mean;
+    3. ``dynamic, mask = vessel_contrast(vessel_mask, bounds, **vessel_kw)``;
+    4. ``static`` is the attenuation where the closed ``mask`` is False and 0 elsewhere.
+    ``static + dynamic`` is the reference's ``full_volume``.  The reference zeroes its vessel-free volume (``raw-no-vessel``) with the
+    segmentation as given; here the CLOSED mask is used, so that the pair sums to the full volume and no attenuation is counted twice
+    under the contrast.  ``static[p]`` with ``dynamic`` (or ``dynamic[p:p+1]``) and ``bounds`` are what ``drr.project_sequence``,
+    ``drr.volume_teacher`` and ``drr.fit_volumes`` take."""
+    who = "prepare_ccta"
+    _metrics._check_volume(raw_hu, who, "raw_hu")
+    m = _mask_input(vessel_mask, who)
+    if raw_hu.dim() not in (3, 4) or m.shape != raw_hu.shape or m.device != raw_hu.device:
+        raise _capi.NcaError(f"{who} takes raw_hu and vessel_mask [P, n0, n1, n2] or [n0, n1, n2] of one shape on one device, got {tuple(raw_hu.shape)} and "
+                             f"{tuple(m.shape)}")
+    att = _attenuation64(raw_hu.detach())          # f64 until the aorta is filled in: one rounding to f32
+    if labels is not None:
+        if aorta_label is None or heart_label is None:
+            raise _capi.NcaError(f"{who}: labels need aorta_label and heart_label")
+        if not isinstance(labels, torch.Tensor) or labels.shape != raw_hu.shape or labels.device != raw_hu.device:
+            raise _capi.NcaError(f"{who}: labels is a tensor of the shape and device of raw_hu, {tuple(raw_hu.shape)}")
+        heart, aorta = labels == heart_label, labels == aorta_label
+        dims = (-3, -2, -1)
+        mean = torch.where(heart, att, torch.zeros((), dtype=torch.float64, device=att.device)).sum(dim=dims, keepdim=True) / heart.sum(dim=dims, keepdim=True)
+        att = torch.where(aorta, mean, att)
+    elif aorta_label is not None or heart_label is not None:
+        raise _capi.NcaError(f"{who}: aorta_label and heart_label need labels")
+    dynamic, closed = vessel_contrast(m, bounds, **vessel_kw)
+    static = torch.where(closed, torch.zeros((), dtype=torch.float32, device=att.device), att.to(torch.float32))
+    return {"static": static, "dynamic": dynamic, "mask": closed, "bounds": tuple((float(b[0]), float(b[1])) for b in bounds)}

@@ -279,7 +279,7 @@ def mask_distance_reductions(a: torch.Tensor, b: torch.Tensor, dist_to_a: torch.
 
 @torch.no_grad()
 def mask_distances(pred: torch.Tensor, truth: torch.Tensor, bounds, *, threshold: float, pred_threshold: Optional[float] = None,
-                   percentile: float = 95.0) -> dict:
+                   percentile: float = 95.0, surface: bool = False) -> dict:
     """Distances between the masks ``A = pred > pred_threshold`` (``threshold`` when ``pred_threshold`` is ``None``) and
     ``B = truth > threshold`` of two f32 stacks ``[..., n0, n1, n2]`` on the device, in the world units of ``bounds``: f64 device tensors of
     the leading shape (a stack ``[P, n0, n1, n2]`` gives ``[P]``).
@@ -289,8 +289,13 @@ def mask_distances(pred: torch.Tensor, truth: torch.Tensor, bounds, *, threshold
     larger of the two directed maxima; ``hd_percentile``: the larger of the two directed ``percentile`` quantiles
     (``torch.quantile(..., interpolation="higher")``).  The masks are whole bodies, not surfaces: a node of A inside B counts with distance 0.
 
-    Two ``distance_transform`` calls; the reductions are torch on the device.  An entry whose A or B is empty is NaN in every distance
-    (its counts are still returned); identical masks give exactly 0 in every distance."""
+    ``surface=True`` measures between SURFACES instead: A and B are first replaced by their borders, ``ccta.mask_border`` (the nodes one
+    6-connected erosion removes; a node of a mask on a face of the grid is a border node), and everything above -- the two distance maps, the
+    reductions, and the counts ``n_pred`` and ``n_truth`` -- is taken of those.  This is MedPy's ``__surface_distances`` with connectivity
+    1, on which its ``assd`` and ``hd95`` rest: a prediction lying wholly inside the truth no longer scores 0.
+
+    Two ``distance_transform`` calls (and, with ``surface``, two ``ccta.mask_border``); the reductions are torch on the device.  An entry
+    whose A or B is empty is NaN in every distance (its counts are still returned); identical masks give exactly 0 in every distance."""
     _check_volume(pred, "mask_distances", "pred")
     _check_volume(truth, "mask_distances", "truth")
     if pred.shape != truth.shape:
@@ -299,6 +304,12 @@ def mask_distances(pred: torch.Tensor, truth: torch.Tensor, bounds, *, threshold
         raise _capi.NcaError(f"mask_distances: pred lives on {pred.device}, truth on {truth.device}")
     threshold = float(threshold)
     pred_threshold = threshold if pred_threshold is None else float(pred_threshold)
+    if surface:
+        from . import ccta          # ccta imports this module
+        a, b = ccta.mask_border(pred, threshold=pred_threshold), ccta.mask_border(truth, threshold=threshold)
+        to_a = distance_transform(a.to(torch.float32), bounds, threshold=0.5)
+        to_b = distance_transform(b.to(torch.float32), bounds, threshold=0.5)
+        return mask_distance_reductions(a, b, to_a, to_b, percentile)
     to_a = distance_transform(pred, bounds, threshold=pred_threshold)
     to_b = distance_transform(truth, bounds, threshold=threshold)
     return mask_distance_reductions(pred.detach() > pred_threshold, truth.detach() > threshold, to_a, to_b, percentile)

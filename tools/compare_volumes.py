@@ -7,7 +7,8 @@ Each directory holds static.npy [n0,n1,n2] and / or dynamic.npy [P,n0,n1,n2] as 
 the first is the prediction, the second the truth.  For every file both hold: phantom.volume_errors (RMSE over all nodes, Dice of the masks
 > threshold) and metrics.mask_distances (mean, Hausdorff and percentile distances between the masks, in the world units of --bounds, per
 volume of the stack).  --pred-threshold thresholds the prediction at a value of its own (a sparse-view fit rarely reaches the truth's
-densities); --pred-fraction F sets it to F times the prediction's own maximum instead.  Prints one JSON record, and writes it with --out.
+densities); --pred-fraction F sets it to F times the prediction's own maximum instead.  --surface measures between the borders of the two
+masks (metrics.mask_distances(surface=True)) and marks the record with "surface": true.  Prints one JSON record, and writes it with --out.
 """
 import argparse
 import json
@@ -43,17 +44,20 @@ def parser():
     ap.add_argument("--pred-threshold", type=float, default=None, help="threshold of the prediction (default: --threshold)")
     ap.add_argument("--pred-fraction", type=float, default=None, help="threshold the prediction at this fraction of its own maximum")
     ap.add_argument("--percentile", type=float, default=95.0)
+    ap.add_argument("--surface", action="store_true", help="measure between the borders of the masks (MedPy's surface distances), not between whole bodies")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--out", default=None, help="also write the record to this file")
     return ap
 
 
-def compare(pred, truth, bounds, threshold, pred_threshold, percentile):
+def compare(pred, truth, bounds, threshold, pred_threshold, percentile, surface=False):
     """The record of one pair of device tensors of one shape."""
     from nerfca_amd import metrics, phantom
     rec = phantom.volume_errors(pred, truth, threshold)
     rec["pred_threshold"] = threshold if pred_threshold is None else pred_threshold
-    dist = metrics.mask_distances(pred, truth, bounds, threshold=threshold, pred_threshold=pred_threshold, percentile=percentile)
+    if surface:
+        rec["surface"] = True
+    dist = metrics.mask_distances(pred, truth, bounds, threshold=threshold, pred_threshold=pred_threshold, percentile=percentile, surface=surface)
     rec.update({k: v.reshape(-1).tolist() for k, v in dist.items()})
     return rec
 
@@ -72,7 +76,7 @@ def main(argv=None):
         if pred.shape != truth.shape:
             sys.exit(f"compare_volumes: {a} is {tuple(pred.shape)}, {b} is {tuple(truth.shape)}")
         pthr = args.pred_threshold if args.pred_fraction is None else args.pred_fraction * float(pred.max())
-        out[name] = compare(pred, truth, args.bounds, args.threshold, pthr, args.percentile)
+        out[name] = compare(pred, truth, args.bounds, args.threshold, pthr, args.percentile, args.surface)
     if not any(n in out for n in NAMES):
         sys.exit(f"compare_volumes: {args.pred} and {args.truth} share neither static.npy nor dynamic.npy")
     text = json.dumps(out, indent=1)
