@@ -849,6 +849,61 @@ int nca_vol_cityblock(const NcaGrid* grid, const float* vol, int32_t n_vol, doub
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_filt_last_error(void);
 
+/* ---- resample: the cubic-spline zoom of voxel stacks (ccta.spline_filter / zoom / resample, resample= of ccta.prepare_ccta) ---------------
+ * What the reference takes from scipy.ndimage.zoom(x, f, order=3) (mode "constant", prefilter, grid_mode False) to bring a CT and its
+ * segmentations to unit spacing (preprocess/preprocess_ccta.py:57-60), and order 0 beside it.  Purely additive to ABI 13.  Like the other
+ * view sections these entry points keep their OWN per-thread message (the accessor below); a refused call launches nothing and reads no
+ * device pointer; a launch failure is reported once.  vol is f32 [n_vol][n0][n1][n2] contiguous on the device, on one NcaGrid (`grid` is a
+ * host pointer; lo and inv are validated but unused: the zoom counts in nodes).  Every volume is resampled on its own.  Every operation below
+ * is ONE rounded f64 operation in the order written (the kernels spell each one out: nothing leans on a contraction flag).
+ *
+ * PREFILTER (order 3).  c = (double)vol, exact.  The axes are taken in the order 0, 1, 2, each on the result of the one before.  On the host,
+ * once:  z = sqrt(3.0) - 2.0;   gain = (1 - z) * (1 - 1 / z);   and for a line of n nodes zn = z multiplied by z another n - 2 times (zn = z
+ * at n = 2; no pow).  They travel as kernel arguments.  Then, for every line of the axis:
+ *     c[i] = c[i] * gain                                     for every i
+ *     s = c[0] + zn * c[n-1];   zi = z
+ *     for i = 1 .. n-2:   s = s + zi * (c[i] + zn * c[n-1-i]);   zi = zi * z
+ *     c[0] = s / (1 - zn * zn)
+ *     for i = 1 .. n-1:   c[i] = c[i] + z * c[i-1]
+ *     c[n-1] = ((z * c[n-2] + c[n-1]) * z) / (z * z - 1)
+ *     for i = n-2 .. 0:   c[i] = z * (c[i+1] - c[i])
+ * This is scipy's ni_splines.c for the mirror boundary, which mode "constant" uses for the prefilter.  A line is serial by definition; one
+ * thread owns a line and the parallelism is across lines.  Three launches (axis 0: f32 -> f64, axes 1 and 2 in place in coeff), each staging
+ * sixteen whole lines in LDS, so an axis has at most NCA_EDT_MAX_AXIS nodes.  nca_vol_spline_filter writes c as f64 [n_vol][n0][n1][n2].
+ * Against scipy.ndimage.spline_filter (whose build contracts some of these operations) c is a few f64 units off: at most 2^-44 of the
+ * largest |vol| (tests/test_resample_cpu.py measures about 2^-47); the library is held to the definition above bit for bit.
+ *
+ * INTERPOLATION.  m: HOST int32 [3], the output's nodes per axis, every m[a] >= 2; out is f32 [n_vol][m0][m1][m2].  Per axis, on the host,
+ * step_a = (n_a - 1) / (m_a - 1) in f64: end nodes map to end nodes.  For output index o of an axis:
+ *     cc = min((double)o * step_a, (double)(n_a - 1))
+ * order 3:   f = floor(cc);   y = cc - f;   t = 1 - y;
+ *     w1 = (y*y*(y-2)*3+4)/6;   w2 = (t*t*(t-2)*3+4)/6;   w0 = t*t*t/6;   w3 = 1 - w0 - w1 - w2     (each left to right)
+ *     the taps f-1 .. f+2, mirrored onto the line: j = M(f - 1 + k), M(i) = q if q <= n-1, else 2(n-1) - q, with q = i mod 2(n-1) in 0 .. 2n-3;
+ *     acc = 0;   for k0, k1, k2 in lexicographic order:   acc = acc + ((c[j0][j1][j2] * w_k0) * w_k1) * w_k2;
+ *     out = (float)acc: the one rounding to f32.
+ * order 0:   one tap floor(cc + 0.5) per axis, no prefilter, out = vol at that node: exact, a NaN or an infinity included.
+ * With the coefficients given, order 3 has the bits of scipy.ndimage.zoom(c, f, order=3, prefilter=False) and order 0 those of
+ * zoom(x, f, order=0), for every size pair scipy does not overshoot at.  DELIBERATELY NOT scipy's: the min in cc.  Where (m_a - 1) * step_a
+ * lands one ulp above n_a - 1 (4 -> 188 nodes, and about 4 % of all pairs), scipy takes the last output plane of that axis for outside the
+ * volume and writes 0 into it; here the last output node is the last input node.  Orders 1, 2, 4 and 5, other boundary modes and grid_mode
+ * are not offered.
+ * nca_vol_zoom at order 3 runs the prefilter into the workspace (8 bytes per input node, rounded up to a multiple of 256) and then one
+ * launch with a thread per output node, which forms cc, the weights and the taps from step_a: no tables.  Order 0 is that one launch and
+ * needs no workspace (work may be NULL).  Every node of every stage is written once by one thread: no atomics, the same bits on every run.
+ * out may NOT alias vol.  The query returns the workspace in bytes (0 at order 0), and 0 for arguments the entry point refuses.
+ * NCA_E_INVALID (the message names the value): a NULL grid, vol, coeff, m or out; coeff == vol, out == vol; n_vol <= 0; the grid refusals of
+ * nca_drr_project; m[a] < 2; an order other than 0 or 3; output nodes whose bytes overflow int64 or that need more than 2^24 workgroups of
+ * 256 threads; more than 2^24 workgroups in one of the prefilter's launches (tiles of 16 lines).  NCA_E_UNSUPPORTED: at order 3 (and for
+ * nca_vol_spline_filter) an axis longer than NCA_EDT_MAX_AXIS.  NCA_E_WORKSPACE: at order 3 work is NULL or work_bytes is below the query's
+ * answer. */
+int nca_vol_spline_filter(const NcaGrid* grid, const float* vol, int32_t n_vol, double* coeff, void* stream);
+size_t nca_vol_zoom_workspace(const NcaGrid* grid_in, int32_t n_vol, int32_t order);
+int nca_vol_zoom(const NcaGrid* grid_in, const float* vol, int32_t n_vol, const int32_t m[3], int32_t order, float* out, void* work, size_t work_bytes,
+                 void* stream);
+
+/* The message of the calling thread's last failed call of this section. */
+const char* nca_resample_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

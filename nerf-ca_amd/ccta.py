@@ -7,10 +7,15 @@ rounding to f32).  ``cityblock_distance`` counts nodes along the axes to the nea
 6-connected structure and any number of iterations.  Both definitions, operation by operation, are in include/nerfca_hip.h ("filt").
 ``vessel_contrast`` and ``prepare_ccta`` chain them with ``metrics.distance_transform`` into the reference's pipeline: a static attenuation
 volume without the vessels and a dynamic vessel-contrast volume, in the shapes ``drr.project_sequence``, ``drr.volume_teacher`` and
-``drr.fit_volumes`` take.  There is no torch implementation behind the two kernels: without the library these functions raise.
+``drr.fit_volumes`` take.  There is no torch implementation behind the kernels: without the library these functions raise.
 
-Not here: the cubic-spline ``zoom`` to unit spacing (volumes come in on the grid of ``bounds``; the distance transform honours anisotropic
-spacings), file readers, other boundary modes, other structuring elements, gradients.
+``zoom`` is ``scipy.ndimage.zoom`` at order 3 (the cubic spline with its prefilter, ``spline_filter``) and order 0, ``resample`` brings a
+volume on ``bounds`` to a target spacing with it, and ``prepare_ccta(resample=...)`` is the reference's resampling to unit spacing
+(preprocess_ccta.py:57-60) before everything that counts in nodes (csrc/view/nca_resample.hip; the definition is in include/nerfca_hip.h,
+"resample").  One deliberate difference from scipy: the last output node of an axis is always the last input node, where scipy writes 0
+into the whole last plane for the size pairs at which its coordinate overshoots by one ulp (4 -> 188 nodes, about 4 % of all pairs).
+
+Not here: spline orders 1, 2, 4 and 5, ``grid_mode``, file readers, other boundary modes, other structuring elements, gradients.
 """
 from __future__ import annotations
 
@@ -26,7 +31,7 @@ from . import fused as _fused
 from . import metrics as _metrics
 
 MAX_RADIUS = 32          # NCA_SMOOTH_MAX_RADIUS
-MAX_AXIS = 512           # NCA_EDT_MAX_AXIS: the city-block transform stages whole lines
+MAX_AXIS = 512           # NCA_EDT_MAX_AXIS: the city-block transform and the spline prefilter stage whole lines
 
 MU_WATER = 0.1494 * 2.5e-2
 MU_AIR = 0.0430 * 2.5e-2
@@ -160,6 +165,103 @@ def mask_border(vol: torch.Tensor, *, threshold: float) -> torch.Tensor:
     return cityblock_distance(_mask_input(vol, "mask_border"), threshold=threshold, inside=True, border=True) == 1
 
 
+def _stack(vol, who):
+    """(grid descriptor, the stack as f32 [n_vol, n0, n1, n2] contiguous, n_vol, shape) of a checked f32 volume stack on the device."""
+    _metrics._check_volume(vol, who)
+    shape = tuple(vol.shape[-3:])
+    desc = _capi.grid_desc(shape, tuple((0.0, float(n - 1)) for n in shape))
+    x = vol.detach().reshape((-1,) + shape).contiguous()
+    return desc, x, x.shape[0], shape
+
+
+@torch.no_grad()
+def spline_filter(vol: torch.Tensor) -> torch.Tensor:
+    """The cubic B-spline coefficients of every volume of the f32 stack ``vol`` ``[..., n0, n1, n2]`` on the device, the prefilter of
+    ``zoom``: an f64 tensor of the same shape.  ``scipy.ndimage.spline_filter(vol, 3, output=float64)`` (mirror boundary) within ``2^-44`` of
+    the largest ``|vol|``; bit for bit the definition in include/nerfca_hip.h ("resample"), the same bits on every run.
+
+    One ``nca_vol_spline_filter`` (three launches; a thread owns a line).  An axis longer than 512 nodes is refused."""
+    desc, x, n_vol, _ = _stack(vol, "spline_filter")
+    out = torch.empty(x.shape, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _capi.check_resample(_capi.lib().nca_vol_spline_filter(C.byref(desc), _capi.ptr(x), n_vol, _capi.ptr(out), _fused._stream()))
+    return out.reshape(vol.shape)
+
+
+def _zoom_shape(shape, zoom, output_shape, who):
+    if output_shape is not None:
+        m = list(output_shape) if isinstance(output_shape, (tuple, list, np.ndarray)) else []
+        if len(m) != 3 or any(int(v) != v for v in m):
+            raise _capi.NcaError(f"{who}: output_shape = {output_shape!r} is not three whole numbers")
+        m = [int(v) for v in m]
+    else:
+        if zoom is None:
+            raise _capi.NcaError(f"{who}: zoom or output_shape is needed")
+        fac = [float(v) for v in _per_axis(zoom, "zoom", who)]
+        if any(not (math.isfinite(f) and f > 0.0) for f in fac):
+            raise _capi.NcaError(f"{who}: zoom = {zoom!r} is not finite and positive")
+        m = [int(round(n * f)) for n, f in zip(shape, fac)]          # Python's round, as scipy
+    for a in range(3):
+        if m[a] < 2:
+            raise _capi.NcaError(f"{who}: axis {a} of the output would have {m[a]} nodes: at least 2 are needed (the input has {shape[a]})")
+    return m
+
+
+@torch.no_grad()
+def zoom(vol: torch.Tensor, zoom=None, *, order: int = 3, output_shape=None) -> torch.Tensor:
+    """``scipy.ndimage.zoom(vol, zoom, order=order)`` (``mode="constant"``, ``prefilter=True``, ``grid_mode=False``) of every volume of the
+    f32 stack ``vol`` ``[..., n0, n1, n2]`` on the device: an f32 tensor ``[..., m0, m1, m2]``.  ``zoom`` is a scalar or one factor per axis
+    and ``m_a = int(round(n_a zoom_a))``; ``output_shape`` ``(m0, m1, m2)`` overrides it.  End nodes map to end nodes: output node ``o`` of an
+    axis lies at ``o (n - 1) / (m - 1)`` on the input.
+
+    ``order=3``: the cubic spline, its prefilter included.  Within ``ulp + 2^-44 max|vol|`` of scipy per node (the interpolation has scipy's
+    bits, the prefilter is a few f64 units off) -- except that the last output node is always the last input node, where scipy writes 0
+    into the last plane for the size pairs at which its coordinate overshoots.  ``order=0``: the nearest node, exact, NaN and infinities
+    included.  Other orders are refused.  At order 3 an axis longer than 512 nodes is refused.
+
+    One ``nca_vol_zoom``: the same bits on every run.  Not differentiable: it runs under ``no_grad`` and the result is detached."""
+    who = "zoom"
+    desc, x, n_vol, shape = _stack(vol, who)
+    if order not in (0, 3) or isinstance(order, bool):
+        raise _capi.NcaError(f"{who}: order = {order!r} is neither 0 nor 3")
+    m = _zoom_shape(shape, zoom, output_shape, who)
+    out = torch.empty((n_vol,) + tuple(m), dtype=torch.float32, device=x.device)
+    lib = _capi.lib()
+    nbytes = int(lib.nca_vol_zoom_workspace(C.byref(desc), n_vol, order))
+    work = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _capi.check_resample(lib.nca_vol_zoom(C.byref(desc), _capi.ptr(x), n_vol, (C.c_int32 * 3)(*m), int(order), _capi.ptr(out), _capi.ptr(work), nbytes,
+                                              _fused._stream()))
+    return out.reshape(tuple(vol.shape[:-3]) + tuple(m))
+
+
+def _zoom_factors(shape, bounds, spacing, who):
+    """``((hi - lo) / (n - 1)) / spacing_a`` per axis: the grid's own spacing over the target's."""
+    _capi.grid_desc(shape, bounds)          # refuses bad bounds
+    target = [float(v) for v in _per_axis(spacing, "spacing", who)]
+    if any(not (math.isfinite(s) and s > 0.0) for s in target):
+        raise _capi.NcaError(f"{who}: spacing = {spacing!r} is not finite and positive")
+    return [((float(b[1]) - float(b[0])) / (n - 1)) / s for b, n, s in zip(bounds, shape, target)], target
+
+
+@torch.no_grad()
+def resample(vol: torch.Tensor, bounds, spacing, *, order: int = 3):
+    """The f32 stack ``vol`` ``[..., n0, n1, n2]`` on the grid of ``bounds`` brought to the node spacing ``spacing`` (a scalar or one value
+    per axis, in the units of ``bounds``): ``(zoom(vol, factors, order=order), bounds)`` with the factors
+    ``((hi - lo) / (n - 1)) / spacing_a``.  The bounds come back unchanged, since end nodes map to end nodes; as the node count is a whole
+    number, the spacing of the result is ``(hi - lo) / (m_a - 1)``, the nearest to ``spacing_a`` that scipy's rule reaches."""
+    who = "resample"
+    _metrics._check_volume(vol, who)
+    fac, _ = _zoom_factors(tuple(vol.shape[-3:]), bounds, spacing, who)
+    return zoom(vol, fac, order=order), tuple((float(b[0]), float(b[1])) for b in bounds)
+
+
+def _round_half_away(x):
+    """What scipy's zoom writes into an integer array: ``trunc(x + 0.5)`` for ``x > 0``, else ``trunc(x - 0.5)``; as f64."""
+    x = x.double()
+    return torch.where(x > 0, x + 0.5, x - 0.5).trunc()
+
+
 def hounsfield_to_attenuation(vol: torch.Tensor, mu_water: float = MU_WATER, mu_air: float = MU_AIR) -> torch.Tensor:
     """``vol / 1000 * (mu_water - mu_air) + mu_water`` (preprocess_ccta.py:7-12), formed in f64 and rounded to f32 once.  Plain torch, on
     whatever device ``vol`` lives on."""
@@ -215,12 +317,20 @@ def vessel_contrast(mask: torch.Tensor, bounds, *, grow: int = 3, shrink: int = 
 
 @torch.no_grad()
 def prepare_ccta(raw_hu: torch.Tensor, vessel_mask: torch.Tensor, bounds, *, labels: Optional[torch.Tensor] = None, aorta_label: Optional[int] = None,
-                 heart_label: Optional[int] = None, **vessel_kw) -> dict:
+                 heart_label: Optional[int] = None, resample=None, label_order: int = 3, **vessel_kw) -> dict:
     """A CT in Hounsfield units ``raw_hu`` and a vessel segmentation ``vessel_mask``, both ``[P, n0, n1, n2]`` (or one volume
-    ``[n0, n1, n2]``) on the device and on the grid of ``bounds``, to the pair of volumes that gets projected (preprocess_ccta.py:54-130
-    without the resampling): ``{"static", "dynamic", "mask", "bounds"}``.
+    ``[n0, n1, n2]``) on the device and on the grid of ``bounds``, to the pair of volumes that gets projected (preprocess_ccta.py:54-130):
+    ``{"static", "dynamic", "mask", "bounds"}``.
 
     1. ``hounsfield_to_attenuation(raw_hu)``;
+    1a. with ``resample`` (a target node spacing in the units of ``bounds``, a scalar or one value per axis; the reference's is 1): the
+       attenuation is brought to that spacing with ``zoom`` at order 3, ``vessel_mask > 0`` and ``labels`` with ``zoom`` at ``label_order``
+       (preprocess_ccta.py:57-60; the factors are those of ``resample``).  At ``label_order=3`` the two segmentations are then rounded half
+       away from zero, which is what scipy does for the reference's integer arrays, and the mask is ``> 0`` after the rounding: a cubic
+       spline through labels invents values between them; ``label_order=0`` takes the nearest node and invents none.  Everything below
+       runs on the new grid, and like the reference (``spacing = (1, 1, 1)`` at :61) it takes the target spacing for the grid's own when it
+       measures the depth inside the vessel; the returned ``bounds`` are the input's, since end nodes map to end nodes.
+       ``resample=None``: no resampling, the volumes stay on the grid they came on;
     2. with ``labels`` (a segmentation of the same shape, any integer or float dtype): the nodes with ``labels == aorta_label`` get the mean
        (f64) of the nodes with ``labels == heart_label`` of the same volume -- NaN if that volume has no heart node, as numpy's mean;
     3. ``dynamic, mask = vessel_contrast(vessel_mask, bounds, **vessel_kw)``;
@@ -241,12 +351,28 @@ def prepare_ccta(raw_hu: torch.Tensor, vessel_mask: torch.Tensor, bounds, *, lab
             raise _capi.NcaError(f"{who}: labels need aorta_label and heart_label")
         if not isinstance(labels, torch.Tensor) or labels.shape != raw_hu.shape or labels.device != raw_hu.device:
             raise _capi.NcaError(f"{who}: labels is a tensor of the shape and device of raw_hu, {tuple(raw_hu.shape)}")
+    elif aorta_label is not None or heart_label is not None:
+        raise _capi.NcaError(f"{who}: aorta_label and heart_label need labels")
+    depth_bounds = bounds
+    if resample is not None:
+        if label_order not in (0, 3) or isinstance(label_order, bool):
+            raise _capi.NcaError(f"{who}: label_order = {label_order!r} is neither 0 nor 3")
+        fac, target = _zoom_factors(tuple(raw_hu.shape[-3:]), bounds, resample, who)
+
+        def labels_to_grid(x):
+            y = zoom(x, fac, order=label_order)
+            return _round_half_away(y) if label_order == 3 else y
+
+        att = zoom(att.to(torch.float32), fac, order=3).double()
+        m = (labels_to_grid((m > 0).to(torch.float32)) > 0).to(torch.float32)
+        if labels is not None:
+            labels = labels_to_grid(labels.to(torch.float32))
+        depth_bounds = tuple((float(b[0]), float(b[0]) + (n - 1) * s) for b, n, s in zip(bounds, att.shape[-3:], target))
+    if labels is not None:
         heart, aorta = labels == heart_label, labels == aorta_label
         dims = (-3, -2, -1)
         mean = torch.where(heart, att, torch.zeros((), dtype=torch.float64, device=att.device)).sum(dim=dims, keepdim=True) / heart.sum(dim=dims, keepdim=True)
         att = torch.where(aorta, mean, att)
-    elif aorta_label is not None or heart_label is not None:
-        raise _capi.NcaError(f"{who}: aorta_label and heart_label need labels")
-    dynamic, closed = vessel_contrast(m, bounds, **vessel_kw)
+    dynamic, closed = vessel_contrast(m, depth_bounds, **vessel_kw)
     static = torch.where(closed, torch.zeros((), dtype=torch.float32, device=att.device), att.to(torch.float32))
     return {"static": static, "dynamic": dynamic, "mask": closed, "bounds": tuple((float(b[0]), float(b[1])) for b in bounds)}

@@ -1,6 +1,6 @@
 // nca_view_common.hpp -- what the translation units of csrc/view/ share (internal; nothing here is exported): the error message of a
-// section, the NcaGrid checks of the grid-taking sections (drr project and backproject, vol, phantom, edt, filt), the count of 4 x 8 x 64
-// tiles (vol, phantom), the workspace refusal (ssim, edt, filt) and, for hipcc only, the launch epilogue and the tile's indexing on the device.
+// section, the NcaGrid checks of the grid-taking sections (drr project and backproject, vol, phantom, edt, filt, resample), the count of 4 x 8 x 64
+// tiles (vol, phantom), the workspace refusal (ssim, edt, filt, resample) and, for hipcc only, the launch epilogue and the tile's indexing on the device.
 // Every text below is part of the library's behaviour: tests and callers match on it.
 //
 // The host part is plain C++17 without HIP types: g++ compiles it on its own, as it does nca_rng.hpp.
