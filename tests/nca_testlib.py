@@ -3,13 +3,15 @@ the scalar every render-parity test differentiates,
 
     sum(pix * cp) + 50 sum(sigma_s * cs) + 50 sum(sigma_d * cd),
 
-launch counting, the bf16 bounds, and what the launch-free tests of the view sections (csrc/view/) share: the `capi` / `lib` fixtures, the
+launch counting, the bf16 bounds, the per-entry gradient checks on one-hot upstream gradients (nets with decided ReLU masks, the rank-one
+split, `scaled_err`, the ray and point cases with their memoised oracle gradients), and what the launch-free tests of the view sections (csrc/view/) share: the `capi` / `lib` fixtures, the
 declared-bound-exported check, `refused` and the one list of NcaGrid refusals.  Test modules import from here (and from conftest.py), never from one another.  Every helper
 draws from the generator it is given in a fixed, documented order: the tolerances of the tests were measured on those draws.
 """
 import contextlib
 import ctypes as C
 import dataclasses
+import functools
 import math
 import os
 import re
@@ -157,6 +159,305 @@ def hip_render_grads(s, t, dev, o, d, ph, I0, z, dists, cp, cs, cd, want_depth=F
     if want_depth:
         g["depth"] = zz.grad.detach().clone()
     return pix.detach(), a.detach(), b.detach(), g
+
+
+# ------------------------------------------------------------------------------------------ one-hot upstream gradients
+# (tests/test_onehot_grads_cpu.py, tests/test_onehot_grads_gpu.py.)  With one coefficient at one sample (r*, s*) of one net every weight
+# gradient is the outer product d_l (x) h_{l-1} of that sample: no sum over samples, no cancellation, so every ENTRY can be held to its own
+# row and column scale.  With nets whose ReLU masks are decided by their biases no rounding can flip a mask, on the device or in the oracle.
+def wide_layers(spec):
+    """(weight key, bias key, takes the skip input cat[feats, h]) of every F-wide layer in order."""
+    out = [(f"early_pts_layers.{2 * i}.weight", f"early_pts_layers.{2 * i}.bias", False) for i in range(spec.num_early_layers + 1)]
+    if spec.num_late_layers > 0:
+        out.append(("skip_connection.0.weight", "skip_connection.0.bias", True))
+        out += [(f"late_pts_layers.{2 * i}.weight", f"late_pts_layers.{2 * i}.bias", False) for i in range(spec.num_late_layers - 1)]
+    return out
+
+
+def _bf(x):
+    return x.to(torch.bfloat16).to(x.dtype)
+
+
+def wide_preacts(params, spec, feats, dt=torch.float64, emulate_bf16=True):
+    """The pre-activations [N, F] of every F-wide layer as O.mlp forms them in dtype `dt` (bf16-rounded operands with `emulate_bf16`);
+    feats: the encoded batch (with the gathered latents for a dynamic net)."""
+    rnd = _bf if emulate_bf16 else (lambda x: x)
+    f = feats.to(dt)
+    h, out = f, []
+    for wk, bk, skip in wide_layers(spec):
+        x = torch.cat([f, h], -1) if skip else h
+        z = rnd(x) @ rnd(params[wk].to(dt)).t() + params[bk].to(dt)
+        out.append(z)
+        h = torch.relu(z)
+    return out
+
+
+def decided_params(spec, gen, feats, sign_share=0.25, phases=None):
+    """Seeded parameters whose ReLU masks are decided by the biases: O.init_params(spec, gen), then every F-wide layer in order (early
+    layers, the skip layer with cat[feats, h], late layers) has W divided by max |bf16(W) bf16(h)| over all rows of `feats` (f64
+    accumulation) and bias[f] = +2 or -2 from a seeded draw with at least `sign_share` of the units on each side -- every pre-activation
+    lies in [-3, -1] u [1, 3].  feats: the encoded batch; a dynamic net's latents (drawn here) are gathered by `phases` and appended.
+    The output layer stays as initialised.  Returns (params, [smallest |pre-activation| of each layer], the full input rows)."""
+    p = O.init_params(spec, gen)
+    f = feats.double()
+    if spec.num_time_dim > 0:
+        f = torch.cat([f, p["time_latents"][phases.long()].double()], -1)
+    h, margins = f, []
+    for wk, bk, skip in wide_layers(spec):
+        x = _bf(torch.cat([f, h], -1) if skip else h)
+        P = x @ _bf(p[wk]).double().t()
+        p[wk] = (p[wk].double() / P.abs().max()).float()
+        F = p[wk].shape[0]
+        need = int(math.ceil(sign_share * F))
+        on = torch.rand(F, generator=gen) < 0.5
+        order = torch.randperm(F, generator=gen)
+        for want in (True, False):          # too few of one sign: flip the first units of the seeded order that have the other
+            lack = need - int((on == want).sum())
+            if lack > 0:
+                on[order[on[order] != want][:lack]] = want
+        p[bk] = torch.where(on, 2.0, -2.0).float()
+        z = x @ _bf(p[wk]).double().t() + p[bk].double()
+        margins.append(float(z.abs().min()))
+        h = torch.relu(z)
+    return p, margins, f
+
+
+def onehot_coeffs(R, S, net, r, s):
+    """(cp, cs, cd) of the scalar of oracle_render_grads / hip_render_grads: zero but for 1.0 at [r, s] of the coefficient of `net`
+    ("s": sigma_s, "t": sigma_d)."""
+    cp, cs, cd = torch.zeros(R, dtype=torch.float64), torch.zeros(R, S), torch.zeros(R, S)
+    (cs if net == "s" else cd)[r, s] = 1.0
+    return cp, cs, cd
+
+
+def rank_one_split(dW, db):
+    """Factors of a one-sample weight gradient dW = a (x) u: the row factor a = db, the column factor u = dW[f0] / db[f0] at the row
+    f0 of largest |db|.  In f64."""
+    a = db.detach().double().reshape(-1)
+    W = dW.detach().double().reshape(a.numel(), -1)
+    f0 = int(a.abs().argmax())
+    return a, W[f0] / a[f0]
+
+
+def entry_err(got, want, scale=None):
+    """Largest |got - want| / |scale| over the entries (scale: `want` itself when None), and its index; an entry whose scale is zero must be
+    equal bit for bit (else inf)."""
+    got, want = got.detach().double().cpu(), want.detach().double().cpu()
+    sc = (want if scale is None else scale.detach().double().cpu()).abs().expand_as(want)
+    diff = (got - want).abs()
+    e = torch.where(sc > 0, diff / sc.clamp_min(1e-300), torch.where(diff > 0, torch.full_like(diff, math.inf), torch.zeros_like(diff)))
+    e = torch.where(torch.isfinite(got), e, torch.full_like(e, math.inf))
+    i = int(e.argmax())
+    return float(e.flatten()[i]), tuple(int(v) for v in torch.unravel_index(torch.tensor(i), e.shape)) if e.dim() else ()
+
+
+def rank_one_err(dW, db):
+    """Check A: the largest relative distance of an entry of dW from db[f] u[j] (rank_one_split), and its (row, column)."""
+    a, u = rank_one_split(dW, db)
+    return entry_err(dW.reshape(a.numel(), -1), a[:, None] * u[None, :])
+
+
+def scaled_err(got, want, a, c=None):
+    """Check C's metric.  A weight gradient [F, K] with the oracle's row factor a and column factor c: per entry
+    |got - want| / (max |a| max(|c_j|, 2^-8 max |c|)) -- columns at their own scale down to 1/256 of the largest, rows at the layer's
+    largest delta (a delta is a sum with cancellation even for one sample: a per-row relative measure would be noise).  A bias-like
+    vector (c None): |got - want| / max |a|.  Returns the maximum and its index."""
+    got, want = got.detach().double().cpu(), want.detach().double().cpu()
+    amax = float(a.abs().max())
+    if c is None:
+        den = torch.full_like(want, amax)
+    else:
+        c = c.detach().double().abs()
+        den = (amax * torch.maximum(c, c.max() * 2.0 ** -8))[None, :].expand_as(want.reshape(-1, c.numel())).reshape(want.shape)
+    return entry_err(got, want, den)
+
+
+ONEHOT_R = 9
+ONEHOT_NETS = {"F32_e1": (32, 1, 0), "F64_e2": (64, 2, 0), "F128_e3": (128, 3, 0), "F128_e1_l2": (128, 1, 2), "F32_e0_l1": (32, 0, 1)}   # (F, early, late of the static net)
+# (net, S, iteration of the dynamic net's band window) of every ray batch of the one-hot tests.  S = 70: two wave tiles per ray, the second
+# with 6 samples; 130: three tiles, the last with 2; 30 000: a window of its own for the dynamic net (the input block is not shared)
+ONEHOT_RAY_CASES = [(n, 70, 75000) for n in ONEHOT_NETS] + [("F64_e2", 130, 75000), ("F128_e3", 70, 30000)]
+ONEHOT_POINT_CASES = [("F32_e1", 130), ("F128_e3", 130), ("F128_e1_l2", 130), ("F144_e1", 300)]          # F = 144: the general kernels
+ONEHOT_POINT_NETS = dict(ONEHOT_NETS, F144_e1=(144, 1, 0))
+BF_FACTOR = 2.0 ** -6          # check C, bf16 operands: one bf16 step is at most 2^-7 of a value, once on each factor
+
+
+def onehot_launches(S):
+    """[((r, s) of the static net's one-hot, (r, s) of the dynamic net's)]: the sample positions are both 32-column halves of a wave tile,
+    their edges, the first sample of the ragged tile and its last; the rays 0, R - 1 and 4.  The two nets' one-hots of a launch sit at
+    different rays (and samples)."""
+    pos = list(zip((0, ONEHOT_R - 1, 4, 0, ONEHOT_R - 1, 4), (0, 31, 32, 63, 64, S - 1)))
+    return [(pos[i], pos[(i + 1) % 6]) for i in range(6)]
+
+
+def onehot_emulations(S):
+    """NetSpec fields of the oracle that rounds what each backward plan rounds."""
+    return {"f32": {}, "recompute": dict(emulate_bf16=True, emulate_stage_formats=None),
+            "bf16_store": dict(emulate_bf16=True, emulate_fp8_stage=S, emulate_stage_formats=("bf16", "bf16")),
+            "fp8_store": dict(emulate_bf16=True, emulate_fp8_stage=S)}
+
+
+def onehot_factor_errs(spec, got, want):
+    """Check C over one net: [(parameter name, scaled_err, index)] of every parameter of `got` against the oracle's `want`: weights of the
+    F-wide layers with the oracle's row and column factors, biases at the layer's largest delta, the output layer and the latents in
+    the vector form at their own largest entry."""
+    out = []
+    for wk, bk, _ in wide_layers(spec):
+        a, c = rank_one_split(want[wk], want[bk])
+        out.append((wk,) + scaled_err(got[wk], want[wk], a, c))
+        out.append((bk,) + scaled_err(got[bk], want[bk], a))
+    for k in want:
+        if k.startswith("output_linear") or k == "time_latents":
+            out.append((k,) + scaled_err(got[k], want[k], want[k].double()))
+    return out
+
+
+class _OnehotOracle:
+    """Memo of the oracle's one-hot gradients of a pair of nets and of check C's floor."""
+
+    def __init__(self):
+        self._memo = {}
+
+    def spec(self, net):
+        return self.ss if net == "s" else self.sd
+
+    def params(self, net):
+        return self.ps if net == "s" else self.pd
+
+    def oracle(self, i, emu, dt=torch.float64):
+        """{"s." / "t." + parameter name: gradient} of one-hot launch i, from the oracle with the roundings of plan `emu` in dtype dt."""
+        key = (i, emu, dt)
+        if key not in self._memo:
+            self._memo[key] = self._run(i, emu, dt)
+        return self._memo[key]
+
+    def floor(self, i, emu):
+        """{prefixed parameter name: scaled_err of the f32 emulating oracle from the f64 one}: the floor of check C."""
+        g32, g64 = self.oracle(i, emu, torch.float32), self.oracle(i, emu)
+        out = {}
+        for net in self.nets:
+            sub = lambda g: {k[2:]: v for k, v in g.items() if k[0] == net}          # noqa: E731
+            out.update({net + "." + k: e for k, e, _ in onehot_factor_errs(self.spec(net), sub(g32), sub(g64))})
+        return out
+
+
+class OnehotRays(_OnehotOracle):
+    """A static / dynamic pair of decided nets on one seeded batch of ONEHOT_R rays x S samples."""
+    nets = "st"
+
+    def __init__(self, name, S, it_d):
+        super().__init__()
+        F, early, late = ONEHOT_NETS[name]
+        self.name, self.S, self.it_d, self.F, self.early, self.late = name, S, it_d, F, early, late
+        self.early_d = max(early, 1)          # the dynamic net is plain (a Temporal with late layers has no output in the reference)
+        gen = torch.Generator().manual_seed(9100 + 7 * F + 3 * early + late + S + it_d // 1000)
+        self.ss, self.sd = spec_from(F, early, late), spec_from(F, self.early_d, 0, T=8)
+        self.win, self.win_d = O.freq_mask_alpha(12, 75000, 150000, 1)[0], O.freq_mask_alpha(12, it_d, 150000, 1)[0]
+        self.o, self.d, self.ph, self.z, self.I0 = ray_inputs(ONEHOT_R, S, gen)[:5]
+        self.dists = O.ray_dists(self.z, torch.float64)
+        pts = O.query_points(self.o, self.d, self.z)
+        self.ps, self.margin_s, self.feats_s = decided_params(self.ss, gen, O.encode(pts, self.ss, self.win))
+        self.pd, self.margin_d, self.feats_d = decided_params(self.sd, gen, O.encode(pts, self.sd, self.win_d), phases=self.ph[:, None].repeat(1, S).flatten())
+        self.launches = onehot_launches(S)
+
+    def feats(self, net, r, s):
+        """The f64 input row (the encoded f32 query point, then the latents) of sample (r, s)."""
+        return (self.feats_s if net == "s" else self.feats_d)[r * self.S + s]
+
+    def coeffs(self, i):
+        """(cp, cs, cd) of launch i over the whole batch."""
+        (rs, s_s), (rd, s_d) = self.launches[i]
+        cp, cs, _ = onehot_coeffs(ONEHOT_R, self.S, "s", rs, s_s)
+        return cp, cs, onehot_coeffs(ONEHOT_R, self.S, "t", rd, s_d)[2]
+
+    def _run(self, i, emu, dt):
+        # the oracle runs on the launch's two rays only: rays are independent and tile scales are per ray
+        (rs, s_s), (rd, s_d) = self.launches[i]
+        rows = torch.tensor([rs, rd])
+        cs, cd = onehot_coeffs(2, self.S, "s", 0, s_s)[1], onehot_coeffs(2, self.S, "t", 1, s_d)[2]
+        pso, pdo = oracle_render_grads(self.ps, self.ss, self.pd, self.sd, self.win, self.o[rows], self.d[rows], self.ph[rows], self.I0[rows], self.z,
+                                       torch.zeros(2, dtype=torch.float64), cs, cd, dt=dt, win_d=self.win_d, emulate=onehot_emulations(self.S)[emu])[4:]
+        return {k: v.detach() for k, v in prefixed_grads(pso, pdo).items()}
+
+
+class OnehotPoints(_OnehotOracle):
+    """Decided nets on N seeded points for CPPN.forward / Temporal.forward_composite; launch i puts the one-hot `gout` at ns[i] (static
+    net) and ns[i - 1] (dynamic net: a plain one beside a static net with a skip layer)."""
+
+    def __init__(self, name, N):
+        super().__init__()
+        F, early, late = ONEHOT_POINT_NETS[name]
+        self.name, self.N, self.F, self.early, self.late, self.early_d = name, N, F, early, late, max(early, 1)
+        gen = torch.Generator().manual_seed(9700 + 7 * F + 3 * early + late + N)
+        self.ss, self.sd = spec_from(F, early, late), spec_from(F, self.early_d, 0, T=8)
+        self.win = O.freq_mask_alpha(12, 75000, 150000, 1)[0]
+        self.x = torch.rand(N, 3, generator=gen) * 2 - 1
+        self.ts = torch.randint(0, 10, (N,), generator=gen)
+        self.ps, self.margin_s, self.feats_s = decided_params(self.ss, gen, O.encode(self.x, self.ss, self.win))
+        self.pd, self.margin_d, self.feats_d = decided_params(self.sd, gen, O.encode(self.x, self.sd, self.win), phases=self.ts)
+        self.nets = "st"
+        self.ns = [0, 63, 64, 129] if N == 130 else [0, 127, 128, N - 1]
+        self.launches = [(self.ns[i], self.ns[i - 1]) for i in range(4)]
+
+    def feats(self, net, n):
+        return (self.feats_s if net == "s" else self.feats_d)[n]
+
+    def _run(self, i, emu, dt):
+        out = {}
+        for net, n in zip("st", self.launches[i]):
+            spec = dataclasses.replace(self.spec(net), emulate_bf16=emu != "f32")
+            p = {k: v.clone().to(dt).requires_grad_(True) for k, v in self.params(net).items()}
+            x = self.x[n:n + 1].to(dt)
+            y = O.static_forward(p, spec, x, self.win.to(dt)) if net == "s" else O.dynamic_forward(p, spec, x, self.ts[n:n + 1], self.win.to(dt))
+            y.sum().backward()
+            out.update({net + "." + k: v.grad.detach() for k, v in p.items()})
+        return out
+
+
+@functools.lru_cache(maxsize=None)
+def onehot_rays(name, S=70, it_d=75000):
+    return OnehotRays(name, S, it_d)
+
+
+@functools.lru_cache(maxsize=None)
+def onehot_points(name, N):
+    return OnehotPoints(name, N)
+
+
+def onehot_latent_rows(tl, phase, tag):
+    """Check B on d loss / d time_latents [10, T] of a one-hot at a sample of heart phase `phase`: every other row is zero bit for bit."""
+    rest = tl.detach().cpu()[torch.arange(tl.shape[0]) != phase]
+    assert not bool(rest.any()), (tag, "time_latents", "B: latent rows", torch.nonzero(rest)[:4].tolist())
+    assert bool(tl[phase].detach().cpu().any()), (tag, "time_latents", "the sample's own row is zero")
+
+
+def onehot_checks_ab(spec, params, g, x, tag, deltas_nonzero=True):
+    """Checks A and B on one net's one-hot gradients g = {parameter name: gradient} for the sample with input row x (f64, the oracle's):
+    every F-wide layer's weight gradient is db (x) u to 2^-20 per entry (one sample's entry is one product -- at most nine partial products of
+    the exact 3-way bf16 split in f32 mode -- so sixteen f32 roundings is generous; a skip layer: over its K0 + F columns); rows of off
+    units (the bias is -2), columns whose input is exactly zero (an off unit of the previous layer, an encoded feature that is zero) are
+    zero bit for bit; everything is finite.  Returns the worst check-A error."""
+    worst = 0.0
+    h, f = x, x
+    for k, v in g.items():
+        assert bool(torch.isfinite(v).all()), (tag, k)
+    for wk, bk, skip in wide_layers(spec):
+        xin = torch.cat([f, h]) if skip else h
+        dW, db = g[wk].cpu(), g[bk].cpu()
+        off = params[bk] < 0
+        assert off.any() and not off.all()
+        assert not bool(db[off].any()) and not bool(dW[off].any()), (tag, wk, "B: off-unit rows", torch.nonzero(dW[off])[:4].tolist())
+        assert not deltas_nonzero or bool((db[~off] != 0).all()), (tag, bk, "an on unit without a delta")          # (an e5m2 delta may underflow)
+        assert not bool(dW[:, xin == 0].any()), (tag, wk, "B: columns of zero inputs", torch.nonzero(dW[:, xin == 0])[:4].tolist())
+        e, at = rank_one_err(dW, db)
+        assert e <= 2.0 ** -20, (tag, wk, "A: row, column", at, e)
+        worst = max(worst, e)
+        h = torch.relu(_bf(xin) @ _bf(params[wk]).double().t() + params[bk].double())          # (only its zeros are used)
+    dWo, dbo = g["output_linear.0.weight"].cpu(), g["output_linear.0.bias"].cpu()
+    assert not bool(dWo[:, h == 0].any()), (tag, "output_linear.0.weight", "B: columns of off units")
+    e, at = rank_one_err(dWo, dbo)
+    assert e <= 2.0 ** -20, (tag, "output_linear.0.weight", at, e)
+    return max(worst, e)
 
 
 def oracle_fine_sampler(sig_s, sig_d, z, u, reduce_max=None):
