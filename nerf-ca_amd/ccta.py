@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from . import _view
 from . import fused as _fused
 from . import metrics as _metrics
 
@@ -78,23 +79,19 @@ def gaussian_filter(vol: torch.Tensor, sigma, *, radius=None, truncate: float = 
 
     One ``nca_vol_smooth`` (three launches, f64 intermediates; the summation order is part of the definition in include/nerfca_hip.h,
     "filt"): the same bits on every run.  Not differentiable: it runs under ``no_grad`` and the result is detached."""
-    _metrics._check_volume(vol, "gaussian_filter")
+    _view.check_volume(vol, "gaussian_filter")          # refused before sigma and radius are looked at
     sig = _per_axis(sigma, "sigma", "gaussian_filter")
     rad = _per_axis(radius, "radius", "gaussian_filter")
     halves = [gaussian_weights(s, r, truncate) for s, r in zip(sig, rad)]
-    shape = tuple(vol.shape[-3:])
-    desc = _capi.grid_desc(shape, tuple((0.0, float(n - 1)) for n in shape))
-    x = vol.detach().reshape((-1,) + shape).contiguous()
-    n_vol = x.shape[0]
+    desc, x, n_vol, _ = _view.volume_stack(vol, "gaussian_filter")
     out = torch.empty_like(x)
     c_radius = (C.c_int32 * 3)(*[len(h) - 1 for h in halves])
     flat = np.concatenate(halves)
     c_weights = (C.c_double * flat.size)(*flat.tolist())
     lib = _capi.lib()
     nbytes = int(lib.nca_vol_smooth_workspace(C.byref(desc), n_vol))
-    work = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        _capi.check_filt(lib.nca_vol_smooth(C.byref(desc), _capi.ptr(x), n_vol, c_radius, c_weights, _capi.ptr(out), _capi.ptr(work), nbytes, _fused._stream()))
+    work = _view.workspace(nbytes, x.device)
+    _view.launch(_capi.check_filt, lib.nca_vol_smooth, x.device, C.byref(desc), _capi.ptr(x), n_vol, c_radius, c_weights, _capi.ptr(out), _capi.ptr(work), nbytes)
     return out.reshape(vol.shape)
 
 
@@ -107,21 +104,15 @@ def cityblock_distance(vol: torch.Tensor, *, threshold: float, inside: bool = Fa
     transformed on its own.  ``inside=False`` is ``scipy.ndimage.distance_transform_cdt(~(vol > threshold), metric="taxicab")``.
 
     One ``nca_vol_cityblock`` (three launches, exact in integers): the same bits on every run.  An axis longer than 512 nodes is refused."""
-    _metrics._check_volume(vol, "cityblock_distance")
-    threshold = float(threshold)
-    if math.isnan(threshold):
-        raise _capi.NcaError("cityblock_distance: threshold = nan is not a number")
-    shape = tuple(vol.shape[-3:])
-    desc = _capi.grid_desc(shape, tuple((0.0, float(n - 1)) for n in shape))
-    x = vol.detach().reshape((-1,) + shape).contiguous()
-    n_vol = x.shape[0]
+    _view.check_volume(vol, "cityblock_distance")          # refused before the threshold is looked at
+    threshold = _view.finite_threshold(threshold, "cityblock_distance")
+    desc, x, n_vol, _ = _view.volume_stack(vol, "cityblock_distance")
     out = torch.empty(x.shape, dtype=torch.int32, device=x.device)
     lib = _capi.lib()
     nbytes = int(lib.nca_vol_cityblock_workspace(C.byref(desc), n_vol))
-    work = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        _capi.check_filt(lib.nca_vol_cityblock(C.byref(desc), _capi.ptr(x), n_vol, threshold, 1 if inside else 0, 1 if border else 0, _capi.ptr(out),
-                                               _capi.ptr(work), nbytes, _fused._stream()))
+    work = _view.workspace(nbytes, x.device)
+    _view.launch(_capi.check_filt, lib.nca_vol_cityblock, x.device, C.byref(desc), _capi.ptr(x), n_vol, threshold, 1 if inside else 0, 1 if border else 0,
+                 _capi.ptr(out), _capi.ptr(work), nbytes)
     return out.reshape(vol.shape)
 
 
@@ -130,7 +121,7 @@ def _mask_input(vol, who):
     if isinstance(vol, torch.Tensor) and vol.dtype == torch.bool:
         _fused._require_cuda(vol, "vol")
         vol = vol.to(torch.float32)
-    _metrics._check_volume(vol, who)
+    _view.check_volume(vol, who)
     return vol
 
 
@@ -165,15 +156,6 @@ def mask_border(vol: torch.Tensor, *, threshold: float) -> torch.Tensor:
     return cityblock_distance(_mask_input(vol, "mask_border"), threshold=threshold, inside=True, border=True) == 1
 
 
-def _stack(vol, who):
-    """(grid descriptor, the stack as f32 [n_vol, n0, n1, n2] contiguous, n_vol, shape) of a checked f32 volume stack on the device."""
-    _metrics._check_volume(vol, who)
-    shape = tuple(vol.shape[-3:])
-    desc = _capi.grid_desc(shape, tuple((0.0, float(n - 1)) for n in shape))
-    x = vol.detach().reshape((-1,) + shape).contiguous()
-    return desc, x, x.shape[0], shape
-
-
 @torch.no_grad()
 def spline_filter(vol: torch.Tensor) -> torch.Tensor:
     """The cubic B-spline coefficients of every volume of the f32 stack ``vol`` ``[..., n0, n1, n2]`` on the device, the prefilter of
@@ -181,10 +163,9 @@ def spline_filter(vol: torch.Tensor) -> torch.Tensor:
     the largest ``|vol|``; bit for bit the definition in include/nerfca_hip.h ("resample"), the same bits on every run.
 
     One ``nca_vol_spline_filter`` (three launches; a thread owns a line).  An axis longer than 512 nodes is refused."""
-    desc, x, n_vol, _ = _stack(vol, "spline_filter")
+    desc, x, n_vol, _ = _view.volume_stack(vol, "spline_filter")
     out = torch.empty(x.shape, dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        _capi.check_resample(_capi.lib().nca_vol_spline_filter(C.byref(desc), _capi.ptr(x), n_vol, _capi.ptr(out), _fused._stream()))
+    _view.launch(_capi.check_resample, _capi.lib().nca_vol_spline_filter, x.device, C.byref(desc), _capi.ptr(x), n_vol, _capi.ptr(out))
     return out.reshape(vol.shape)
 
 
@@ -221,17 +202,16 @@ def zoom(vol: torch.Tensor, zoom=None, *, order: int = 3, output_shape=None) -> 
 
     One ``nca_vol_zoom``: the same bits on every run.  Not differentiable: it runs under ``no_grad`` and the result is detached."""
     who = "zoom"
-    desc, x, n_vol, shape = _stack(vol, who)
+    desc, x, n_vol, shape = _view.volume_stack(vol, who)
     if order not in (0, 3) or isinstance(order, bool):
         raise _capi.NcaError(f"{who}: order = {order!r} is neither 0 nor 3")
     m = _zoom_shape(shape, zoom, output_shape, who)
     out = torch.empty((n_vol,) + tuple(m), dtype=torch.float32, device=x.device)
     lib = _capi.lib()
     nbytes = int(lib.nca_vol_zoom_workspace(C.byref(desc), n_vol, order))
-    work = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        _capi.check_resample(lib.nca_vol_zoom(C.byref(desc), _capi.ptr(x), n_vol, (C.c_int32 * 3)(*m), int(order), _capi.ptr(out), _capi.ptr(work), nbytes,
-                                              _fused._stream()))
+    work = _view.workspace(nbytes, x.device)
+    _view.launch(_capi.check_resample, lib.nca_vol_zoom, x.device, C.byref(desc), _capi.ptr(x), n_vol, (C.c_int32 * 3)(*m), int(order), _capi.ptr(out),
+                 _capi.ptr(work), nbytes)
     return out.reshape(tuple(vol.shape[:-3]) + tuple(m))
 
 
@@ -251,7 +231,7 @@ def resample(vol: torch.Tensor, bounds, spacing, *, order: int = 3):
     ``((hi - lo) / (n - 1)) / spacing_a``.  The bounds come back unchanged, since end nodes map to end nodes; as the node count is a whole
     number, the spacing of the result is ``(hi - lo) / (m_a - 1)``, the nearest to ``spacing_a`` that scipy's rule reaches."""
     who = "resample"
-    _metrics._check_volume(vol, who)
+    _view.check_volume(vol, who)
     fac, _ = _zoom_factors(tuple(vol.shape[-3:]), bounds, spacing, who)
     return zoom(vol, fac, order=order), tuple((float(b[0]), float(b[1])) for b in bounds)
 
@@ -340,7 +320,7 @@ def prepare_ccta(raw_hu: torch.Tensor, vessel_mask: torch.Tensor, bounds, *, lab
     under the contrast.  ``static[p]`` with ``dynamic`` (or ``dynamic[p:p+1]``) and ``bounds`` are what ``drr.project_sequence``,
     ``drr.volume_teacher`` and ``drr.fit_volumes`` take."""
     who = "prepare_ccta"
-    _metrics._check_volume(raw_hu, who, "raw_hu")
+    _view.check_volume(raw_hu, who, "raw_hu")
     m = _mask_input(vessel_mask, who)
     if raw_hu.dim() not in (3, 4) or m.shape != raw_hu.shape or m.device != raw_hu.device:
         raise _capi.NcaError(f"{who} takes raw_hu and vessel_mask [P, n0, n1, n2] or [n0, n1, n2] of one shape on one device, got {tuple(raw_hu.shape)} and "

@@ -122,9 +122,9 @@ __global__ void __launch_bounds__(DRR_BLOCK) drr_kernel(NcaGrid g, const float* 
 // The checks both entry points make after their pointers: the counts, the grid with `node_bytes` bytes per node of a volume, and the f64 per
 // ray and volume.  On success *g and *voxels are set.
 static int drr_check(const char* who, const NcaGrid* grid, int32_t n_vol, int64_t R, int32_t S, int node_bytes, NcaGrid* g, int64_t* voxels) {
-    if (n_vol <= 0) return g_err.fail(NCA_E_INVALID, "%s: n_vol = %d is not positive", who, (int)n_vol);
+    NCA_REFUSE_NOT_POSITIVE(g_err, who, "n_vol", n_vol);
     if (R <= 0) return g_err.fail(NCA_E_INVALID, "%s: R = %lld is not positive", who, (long long)R);
-    if (S <= 0) return g_err.fail(NCA_E_INVALID, "%s: S = %d is not positive", who, (int)S);
+    NCA_REFUSE_NOT_POSITIVE(g_err, who, "S", S);
     const int rc = nca_check_grid(g_err, who, grid, n_vol, node_bytes, "volumes", g, voxels);
     if (rc != NCA_OK) return rc;
     if (R > INT64_MAX / 8 / n_vol) return g_err.fail(NCA_E_INVALID, "%s: R = %lld rays x %d volumes overflows int64", who, (long long)R, (int)n_vol);
@@ -147,7 +147,7 @@ static void drr_for_groups(int32_t n_vol, Launch launch) {
 extern "C" int nca_drr_project(const NcaGrid* grid, const float* vol, int32_t n_vol, int64_t R, int32_t S, const double* origins, const double* dirs,
                                const float* z, const double* dists, double i0, double* pix, void* stream) {
     const char* who = "nca_drr_project";
-    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    NCA_REFUSE_NULL_GRID(g_err, who, grid);
     NCA_REFUSE_NULL(g_err, who, vol);
     NCA_REFUSE_NULL(g_err, who, origins);
     NCA_REFUSE_NULL(g_err, who, dirs);
@@ -298,7 +298,7 @@ __global__ void __launch_bounds__(DRR_BLOCK) drr_back_kernel(NcaGrid g, int64_t 
 extern "C" int nca_drr_backproject(const NcaGrid* grid, int32_t n_vol, int64_t R, int32_t S, const double* origins, const double* dirs, const float* z,
                                    const double* dists, const double* g_pix, double* g_vol, void* stream) {
     const char* who = "nca_drr_backproject";
-    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    NCA_REFUSE_NULL_GRID(g_err, who, grid);
     NCA_REFUSE_NULL(g_err, who, origins);
     NCA_REFUSE_NULL(g_err, who, dirs);
     NCA_REFUSE_NULL(g_err, who, z);

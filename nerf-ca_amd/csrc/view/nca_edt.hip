@@ -133,49 +133,37 @@ __global__ void __launch_bounds__(ED_BLOCK) edt_line_kernel(int32_t len, int64_t
     }
 }
 
-// The checks the query and the entry point share; on success *nodes is n_vol n0 n1 n2.
-static int edt_check(const char* who, const NcaGrid* grid, int32_t n_vol, int64_t* nodes) {
-    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
-    if (n_vol <= 0) return g_err.fail(NCA_E_INVALID, "%s: n_vol = %d is not positive", who, (int)n_vol);
-    // the 12 bytes per node of the workspace (and the 4 of the volumes) must fit int64
-    NcaGrid g;
-    int64_t voxels;
-    const int rc = nca_check_grid(g_err, who, grid, n_vol, 16, "volumes", &g, &voxels);
-    if (rc != NCA_OK) return rc;
-    for (int a = 0; a < 3; ++a)
-        if (g.n[a] > NCA_EDT_MAX_AXIS)
-            return g_err.fail(NCA_E_UNSUPPORTED, "%s: n[%d] = %d is longer than NCA_EDT_MAX_AXIS = %d", who, a, (int)g.n[a], (int)NCA_EDT_MAX_AXIS);
-    *nodes = voxels * n_vol;
-    return NCA_OK;
+// The checks the query and the entry point share: the 12 bytes per node of the workspace (and the 4 of the volumes) must fit int64.
+static int edt_check(const char* who, const NcaGrid* grid, int32_t n_vol, NcaGrid* g, int64_t* nodes) {
+    return nca_check_stack(g_err, who, grid, n_vol, "n_vol", 16, "volumes", NCA_EDT_MAX_AXIS, g, nodes);
 }
 
 extern "C" size_t nca_vol_edt_workspace(const NcaGrid* grid, int32_t n_vol) {
+    NcaGrid g;
     int64_t nodes;
-    if (edt_check("nca_vol_edt_workspace", grid, n_vol, &nodes) != NCA_OK) return 0;
+    if (edt_check("nca_vol_edt_workspace", grid, n_vol, &g, &nodes) != NCA_OK) return 0;
     return ((size_t)nodes * 12 + 255) / 256 * 256;
 }
 
 extern "C" int nca_vol_edt(const NcaGrid* grid, const float* vol, int32_t n_vol, double threshold, int32_t invert, float* out, void* work, size_t work_bytes,
                            void* stream) {
     const char* who = "nca_vol_edt";
-    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    NCA_REFUSE_NULL_GRID(g_err, who, grid);
     NCA_REFUSE_NULL(g_err, who, vol);
     NCA_REFUSE_NULL(g_err, who, out);
     if (invert != 0 && invert != 1) return g_err.fail(NCA_E_INVALID, "%s: invert = %d is neither 0 nor 1", who, (int)invert);
     if (threshold != threshold) return g_err.fail(NCA_E_INVALID, "%s: threshold = %g is not a number", who, threshold);
+    NcaGrid g;
     int64_t nodes;
-    const int rc = edt_check(who, grid, n_vol, &nodes);
+    const int rc = edt_check(who, grid, n_vol, &g, &nodes);
     if (rc != NCA_OK) return rc;
-    const NcaGrid g = *grid;
     const int32_t n0 = g.n[0], n1 = g.n[1], n2 = g.n[2];
     const int64_t rows = (int64_t)n_vol * n0 * n1, plane = (int64_t)n1 * n2;
     const int64_t blocks_r = (rows + ED_WAVES - 1) / ED_WAVES;
     const int64_t tiles_1 = (n2 + ED_TC - 1) / ED_TC, blocks_1 = (int64_t)n_vol * n0 * tiles_1;
     const int64_t tiles_0 = (plane + ED_TC - 1) / ED_TC, blocks_0 = (int64_t)n_vol * tiles_0;
-    const int64_t most = blocks_r > blocks_1 ? (blocks_r > blocks_0 ? blocks_r : blocks_0) : (blocks_1 > blocks_0 ? blocks_1 : blocks_0);
-    if (most > ED_MAX_BLOCKS)
-        return g_err.fail(NCA_E_INVALID, "%s: %d volumes of %d x %d x %d voxels make %lld tiles, more than one launch covers", who, (int)n_vol, (int)n0, (int)n1, (int)n2,
-                     (long long)most);
+    const int rcb = nca_check_launch_blocks(g_err, who, n_vol, g, blocks_r, blocks_1, blocks_0, ED_MAX_BLOCKS);
+    if (rcb != NCA_OK) return rcb;
     const int rcw = nca_check_workspace(g_err, who, work, work_bytes, nca_vol_edt_workspace(grid, n_vol));
     if (rcw != NCA_OK) return rcw;
     double w[3];

@@ -106,16 +106,9 @@ __global__ void __launch_bounds__(FL_BLOCK) smooth_row_kernel(int64_t rows, int3
     }
 }
 
-// The checks the query and the entry point share; on success *nodes is n_vol n0 n1 n2.
+// The checks the query and the entry point share: the 16 bytes per node of the workspace and the 4 + 4 of the volumes must fit int64.
 static int smooth_check(const char* who, const NcaGrid* grid, int32_t n_vol, NcaGrid* g, int64_t* nodes) {
-    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
-    if (n_vol <= 0) return g_err.fail(NCA_E_INVALID, "%s: n_vol = %d is not positive", who, (int)n_vol);
-    // the 16 bytes per node of the workspace and the 4 + 4 of the volumes must fit int64
-    int64_t voxels;
-    const int rc = nca_check_grid(g_err, who, grid, n_vol, 24, "volumes", g, &voxels);
-    if (rc != NCA_OK) return rc;
-    *nodes = voxels * n_vol;
-    return NCA_OK;
+    return nca_check_stack(g_err, who, grid, n_vol, "n_vol", 24, "volumes", 0, g, nodes);
 }
 
 extern "C" size_t nca_vol_smooth_workspace(const NcaGrid* grid, int32_t n_vol) {
@@ -128,7 +121,7 @@ extern "C" size_t nca_vol_smooth_workspace(const NcaGrid* grid, int32_t n_vol) {
 extern "C" int nca_vol_smooth(const NcaGrid* grid, const float* vol, int32_t n_vol, const int32_t radius[3], const double* weights, float* out, void* work,
                               size_t work_bytes, void* stream) {
     const char* who = "nca_vol_smooth";
-    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    NCA_REFUSE_NULL_GRID(g_err, who, grid);
     NCA_REFUSE_NULL(g_err, who, vol);
     NCA_REFUSE_NULL(g_err, who, radius);
     NCA_REFUSE_NULL(g_err, who, weights);
@@ -159,10 +152,8 @@ extern "C" int nca_vol_smooth(const NcaGrid* grid, const float* vol, int32_t n_v
     const int32_t lt0 = (n0 + SM_TL - 1) / SM_TL, lt1 = (n1 + SM_TL - 1) / SM_TL, rt = (n2 + SM_TR - 1) / SM_TR;
     // at most 2 nodes / 32 of them per block more than nodes / 64 blocks: far below int64
     const int64_t blocks_0 = (int64_t)n_vol * lt0 * ct0, blocks_1 = (int64_t)n_vol * n0 * lt1 * ct1, blocks_2 = (rows + FL_WAVES - 1) / FL_WAVES * rt;
-    const int64_t most = blocks_0 > blocks_1 ? (blocks_0 > blocks_2 ? blocks_0 : blocks_2) : (blocks_1 > blocks_2 ? blocks_1 : blocks_2);
-    if (most > FL_MAX_BLOCKS)
-        return g_err.fail(NCA_E_INVALID, "%s: %d volumes of %d x %d x %d voxels make %lld tiles, more than one launch covers", who, (int)n_vol, (int)n0, (int)n1, (int)n2,
-                          (long long)most);
+    const int rcb = nca_check_launch_blocks(g_err, who, n_vol, g, blocks_0, blocks_1, blocks_2, FL_MAX_BLOCKS);
+    if (rcb != NCA_OK) return rcb;
     const int rcw = nca_check_workspace(g_err, who, work, work_bytes, nca_vol_smooth_workspace(grid, n_vol));
     if (rcw != NCA_OK) return rcw;
     double* a = (double*)work;          // f64 [nodes] after axis 0, then f64 [nodes] after axis 1
@@ -307,18 +298,9 @@ __global__ void __launch_bounds__(FL_BLOCK) cb_line_kernel(int32_t len, int64_t 
     }
 }
 
+// The checks the query and the entry point share: the 8 bytes per node of the workspace and the 4 + 4 of the volumes must fit int64.
 static int cb_check(const char* who, const NcaGrid* grid, int32_t n_vol, NcaGrid* g, int64_t* nodes) {
-    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
-    if (n_vol <= 0) return g_err.fail(NCA_E_INVALID, "%s: n_vol = %d is not positive", who, (int)n_vol);
-    // the 8 bytes per node of the workspace and the 4 + 4 of the volumes must fit int64
-    int64_t voxels;
-    const int rc = nca_check_grid(g_err, who, grid, n_vol, 16, "volumes", g, &voxels);
-    if (rc != NCA_OK) return rc;
-    for (int a = 0; a < 3; ++a)
-        if (g->n[a] > NCA_EDT_MAX_AXIS)
-            return g_err.fail(NCA_E_UNSUPPORTED, "%s: n[%d] = %d is longer than NCA_EDT_MAX_AXIS = %d", who, a, (int)g->n[a], (int)NCA_EDT_MAX_AXIS);
-    *nodes = voxels * n_vol;
-    return NCA_OK;
+    return nca_check_stack(g_err, who, grid, n_vol, "n_vol", 16, "volumes", NCA_EDT_MAX_AXIS, g, nodes);
 }
 
 extern "C" size_t nca_vol_cityblock_workspace(const NcaGrid* grid, int32_t n_vol) {
@@ -331,7 +313,7 @@ extern "C" size_t nca_vol_cityblock_workspace(const NcaGrid* grid, int32_t n_vol
 extern "C" int nca_vol_cityblock(const NcaGrid* grid, const float* vol, int32_t n_vol, double threshold, int32_t invert, int32_t border, int32_t* out, void* work,
                                  size_t work_bytes, void* stream) {
     const char* who = "nca_vol_cityblock";
-    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    NCA_REFUSE_NULL_GRID(g_err, who, grid);
     NCA_REFUSE_NULL(g_err, who, vol);
     NCA_REFUSE_NULL(g_err, who, out);
     if (invert != 0 && invert != 1) return g_err.fail(NCA_E_INVALID, "%s: invert = %d is neither 0 nor 1", who, (int)invert);
@@ -346,10 +328,8 @@ extern "C" int nca_vol_cityblock(const NcaGrid* grid, const float* vol, int32_t 
     const int64_t blocks_r = (rows + FL_WAVES - 1) / FL_WAVES;
     const int64_t tiles_1 = (n2 + CB_TC - 1) / CB_TC, blocks_1 = (int64_t)n_vol * n0 * tiles_1;
     const int64_t tiles_0 = (plane + CB_TC - 1) / CB_TC, blocks_0 = (int64_t)n_vol * tiles_0;
-    const int64_t most = blocks_r > blocks_1 ? (blocks_r > blocks_0 ? blocks_r : blocks_0) : (blocks_1 > blocks_0 ? blocks_1 : blocks_0);
-    if (most > FL_MAX_BLOCKS)
-        return g_err.fail(NCA_E_INVALID, "%s: %d volumes of %d x %d x %d voxels make %lld tiles, more than one launch covers", who, (int)n_vol, (int)n0, (int)n1, (int)n2,
-                          (long long)most);
+    const int rcb = nca_check_launch_blocks(g_err, who, n_vol, g, blocks_r, blocks_1, blocks_0, FL_MAX_BLOCKS);
+    if (rcb != NCA_OK) return rcb;
     const int rcw = nca_check_workspace(g_err, who, work, work_bytes, nca_vol_cityblock_workspace(grid, n_vol));
     if (rcw != NCA_OK) return rcw;
     int32_t* gd = (int32_t*)work;          // int32 [nodes] after the row pass, then int32 [nodes] after axis 1

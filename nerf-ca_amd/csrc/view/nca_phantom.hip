@@ -151,9 +151,9 @@ extern "C" int nca_phantom_get_cull(void) { return g_ph_cull.load(); }
 extern "C" int nca_phantom_voxelize(const NcaGrid* grid, int32_t n_phase, int32_t n_ell, const double* ell, int32_t n_seg, const double* seg, double rho_v,
                                     double edge, float* out, void* stream) {
     const char* who = "nca_phantom_voxelize";
-    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    NCA_REFUSE_NULL_GRID(g_err, who, grid);
     NCA_REFUSE_NULL(g_err, who, out);
-    if (n_phase <= 0) return g_err.fail(NCA_E_INVALID, "%s: n_phase = %d is not positive", who, (int)n_phase);
+    NCA_REFUSE_NOT_POSITIVE(g_err, who, "n_phase", n_phase);
     if (n_ell < 0) return g_err.fail(NCA_E_INVALID, "%s: n_ell = %d is negative", who, (int)n_ell);
     if (n_seg < 0) return g_err.fail(NCA_E_INVALID, "%s: n_seg = %d is negative", who, (int)n_seg);
     if (n_ell == 0 && n_seg == 0) return g_err.fail(NCA_E_INVALID, "%s: n_ell = 0 and n_seg = 0: there is nothing to rasterise", who);

@@ -106,28 +106,15 @@ __global__ void __launch_bounds__(RS_BLOCK) sp_row_kernel(int64_t rows, int32_t 
     }
 }
 
-// The checks the prefilter, the zoom and its query share; on success *nodes is n_vol n0 n1 n2.  `staged`: the prefilter runs (order 3).
+// The checks the prefilter, the zoom and its query share: the 8 bytes per node of the coefficients and the 4 of the volume must fit int64.
+// `staged`: the prefilter runs (order 3), which stages whole lines and makes three launches of its own.
 static int rs_check(const char* who, const NcaGrid* grid, int32_t n_vol, bool staged, NcaGrid* g, int64_t* nodes) {
-    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
-    if (n_vol <= 0) return g_err.fail(NCA_E_INVALID, "%s: n_vol = %d is not positive", who, (int)n_vol);
-    // the 8 bytes per node of the coefficients and the 4 of the volume must fit int64
-    int64_t voxels;
-    const int rc = nca_check_grid(g_err, who, grid, n_vol, 12, "volumes", g, &voxels);
-    if (rc != NCA_OK) return rc;
-    if (staged) {
-        for (int a = 0; a < 3; ++a)
-            if (g->n[a] > NCA_EDT_MAX_AXIS)
-                return g_err.fail(NCA_E_UNSUPPORTED, "%s: n[%d] = %d is longer than NCA_EDT_MAX_AXIS = %d", who, a, (int)g->n[a], (int)NCA_EDT_MAX_AXIS);
-        const int64_t plane = (int64_t)g->n[1] * g->n[2];
-        const int64_t blocks_0 = (int64_t)n_vol * ((plane + SP_TC - 1) / SP_TC), blocks_1 = (int64_t)n_vol * g->n[0] * ((g->n[2] + SP_TC - 1) / SP_TC);
-        const int64_t blocks_2 = ((int64_t)n_vol * g->n[0] * g->n[1] + SP_TC - 1) / SP_TC;
-        const int64_t most = blocks_0 > blocks_1 ? (blocks_0 > blocks_2 ? blocks_0 : blocks_2) : (blocks_1 > blocks_2 ? blocks_1 : blocks_2);
-        if (most > RS_MAX_BLOCKS)
-            return g_err.fail(NCA_E_INVALID, "%s: %d volumes of %d x %d x %d voxels make %lld tiles, more than one launch covers", who, (int)n_vol, (int)g->n[0],
-                              (int)g->n[1], (int)g->n[2], (long long)most);
-    }
-    *nodes = voxels * n_vol;
-    return NCA_OK;
+    const int rc = nca_check_stack(g_err, who, grid, n_vol, "n_vol", 12, "volumes", staged ? NCA_EDT_MAX_AXIS : 0, g, nodes);
+    if (rc != NCA_OK || !staged) return rc;
+    const int64_t plane = (int64_t)g->n[1] * g->n[2];
+    const int64_t blocks_0 = (int64_t)n_vol * ((plane + SP_TC - 1) / SP_TC), blocks_1 = (int64_t)n_vol * g->n[0] * ((g->n[2] + SP_TC - 1) / SP_TC);
+    const int64_t blocks_2 = ((int64_t)n_vol * g->n[0] * g->n[1] + SP_TC - 1) / SP_TC;
+    return nca_check_launch_blocks(g_err, who, n_vol, *g, blocks_0, blocks_1, blocks_2, RS_MAX_BLOCKS);
 }
 
 static SpConst sp_const(int32_t len) {
@@ -152,7 +139,7 @@ static void sp_launch(const NcaGrid& g, int32_t n_vol, const float* vol, double*
 
 extern "C" int nca_vol_spline_filter(const NcaGrid* grid, const float* vol, int32_t n_vol, double* coeff, void* stream) {
     const char* who = "nca_vol_spline_filter";
-    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    NCA_REFUSE_NULL_GRID(g_err, who, grid);
     NCA_REFUSE_NULL(g_err, who, vol);
     NCA_REFUSE_NULL(g_err, who, coeff);
     if ((const void*)coeff == (const void*)vol) return g_err.fail(NCA_E_INVALID, "%s: coeff is vol: the first launch does not run in place", who);
@@ -243,7 +230,7 @@ extern "C" size_t nca_vol_zoom_workspace(const NcaGrid* grid_in, int32_t n_vol, 
 extern "C" int nca_vol_zoom(const NcaGrid* grid_in, const float* vol, int32_t n_vol, const int32_t m[3], int32_t order, float* out, void* work, size_t work_bytes,
                             void* stream) {
     const char* who = "nca_vol_zoom";
-    if (!grid_in) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    NCA_REFUSE_NULL_GRID(g_err, who, grid_in);
     NCA_REFUSE_NULL(g_err, who, vol);
     NCA_REFUSE_NULL(g_err, who, m);
     NCA_REFUSE_NULL(g_err, who, out);

@@ -1,7 +1,10 @@
 // nca_view_common.hpp -- what the translation units of csrc/view/ share (internal; nothing here is exported): the error message of a
-// section, the NcaGrid checks of the grid-taking sections (drr project and backproject, vol, phantom, edt, filt, resample), the count of 4 x 8 x 64
-// tiles (vol, phantom), the workspace refusal (ssim, edt, filt, resample) and, for hipcc only, the launch epilogue and the tile's indexing on the device.
-// Every text below is part of the library's behaviour: tests and callers match on it.
+// section; for the seven grid-taking sections (drr project and backproject, vol, phantom, edt, filt, resample) the refusals of a NULL descriptor
+// and of a count that is not positive and the NcaGrid checks, and all of them in order as nca_check_stack (edt, filt, resample, whose query and
+// entry point share them); the count of 4 x 8 x 64 tiles (vol, phantom); the largest of three launches' block counts against one launch's limit
+// (edt, filt, resample); the workspace refusal (ssim, edt, filt, resample); and, for hipcc only, the launch epilogue and the tile's indexing on
+// the device.  The Python wrappers' counterpart is nerf-ca_amd/_view.py.  Every text below is part of the library's behaviour: tests and callers
+// match on it.
 //
 // The host part is plain C++17 without HIP types: g++ compiles it on its own, as it does nca_rng.hpp.
 #pragma once
@@ -39,7 +42,18 @@ struct NcaViewErr {
         if (!(p)) return (err).fail(NCA_E_INVALID, "%s: " #p " is NULL", who); \
     } while (0)
 
-// The grid checks, after the caller has refused a NULL `grid` and a `count` (volumes or phases, the `noun`) that is not positive: reserved,
+// "<who>: the grid descriptor is NULL", and "<who>: <name> = <n> is not positive" for an int32 count under the name the header gives it
+#define NCA_REFUSE_NULL_GRID(err, who, grid)                                                      \
+    do {                                                                                          \
+        if (!(grid)) return (err).fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who); \
+    } while (0)
+#define NCA_REFUSE_NOT_POSITIVE(err, who, name, n)                                                                   \
+    do {                                                                                                             \
+        if ((n) <= 0) return (err).fail(NCA_E_INVALID, "%s: %s = %d is not positive", who, name, (int)(n)); \
+    } while (0)
+
+// The grid checks, after the caller has refused a NULL `grid` and a `count` (volumes or phases, the `noun`) that is not positive (the two
+// macros above, or nca_check_stack, which does all three): reserved,
 // then per axis the node count, lo, inv, then that count x n0 n1 n2 nodes of `node_bytes` bytes fit int64.  On success *g is the caller's
 // copy of the descriptor and *voxels = n0 n1 n2.
 inline int nca_check_grid(NcaViewErr& err, const char* who, const NcaGrid* grid, int32_t count, int node_bytes, const char* noun, NcaGrid* g,
@@ -57,6 +71,31 @@ inline int nca_check_grid(NcaViewErr& err, const char* who, const NcaGrid* grid,
         return err.fail(NCA_E_INVALID, "%s: %d %s of %d x %d x %d voxels overflow int64", who, (int)count, noun, (int)g->n[0], (int)g->n[1], (int)g->n[2]);
     *voxels = n01 * g->n[2];
     return NCA_OK;
+}
+
+// Everything a stack of `count` volumes on one grid is checked for, in this order: the descriptor is not NULL, `count` (named `count_name`
+// in the message) is positive, nca_check_grid with `node_bytes` bytes per node, and -- unless max_axis is 0 -- no axis is longer than
+// max_axis = NCA_EDT_MAX_AXIS nodes (the kernels that stage whole lines).  On success *g is the caller's copy and *nodes = count n0 n1 n2.
+inline int nca_check_stack(NcaViewErr& err, const char* who, const NcaGrid* grid, int32_t count, const char* count_name, int node_bytes, const char* noun,
+                           int max_axis, NcaGrid* g, int64_t* nodes) {
+    NCA_REFUSE_NULL_GRID(err, who, grid);
+    NCA_REFUSE_NOT_POSITIVE(err, who, count_name, count);
+    int64_t voxels;
+    const int rc = nca_check_grid(err, who, grid, count, node_bytes, noun, g, &voxels);
+    if (rc != NCA_OK) return rc;
+    for (int a = 0; a < 3 && max_axis; ++a)
+        if (g->n[a] > max_axis)
+            return err.fail(NCA_E_UNSUPPORTED, "%s: n[%d] = %d is longer than NCA_EDT_MAX_AXIS = %d", who, a, (int)g->n[a], max_axis);
+    *nodes = voxels * count;
+    return NCA_OK;
+}
+
+// The three launches of an entry point make b0, b1 and b2 blocks: refused when the largest is more than `cap`, what one launch covers.
+inline int nca_check_launch_blocks(NcaViewErr& err, const char* who, int32_t n_vol, const NcaGrid& g, int64_t b0, int64_t b1, int64_t b2, int64_t cap) {
+    const int64_t most = b0 > b1 ? (b0 > b2 ? b0 : b2) : (b1 > b2 ? b1 : b2);
+    if (most <= cap) return NCA_OK;
+    return err.fail(NCA_E_INVALID, "%s: %d volumes of %d x %d x %d voxels make %lld tiles, more than one launch covers", who, (int)n_vol, (int)g.n[0], (int)g.n[1],
+                    (int)g.n[2], (long long)most);
 }
 
 // A workgroup of vol and phantom owns a tile of 4 x 8 x 64 nodes.  nb[a] = ceil(n[a] / tile[a]) and *tiles = nb0 nb1 nb2 of a checked

@@ -157,9 +157,9 @@ __global__ void __launch_bounds__(TV_BLOCK) voltv_kernel(NcaGrid g, const float*
 // The checks both entry points share, after their own pointers; on success *voxels and the tiles per axis are set.
 static int vol_check(const char* who, const NcaGrid* grid, const float* vol, int32_t n_vol, double eps_s, double eps_t, int32_t cyclic, NcaGrid* g,
                      int64_t* voxels, int32_t nb[3], int64_t* tiles) {
-    if (!grid) return g_err.fail(NCA_E_INVALID, "%s: the grid descriptor is NULL", who);
+    NCA_REFUSE_NULL_GRID(g_err, who, grid);
     NCA_REFUSE_NULL(g_err, who, vol);
-    if (n_vol <= 0) return g_err.fail(NCA_E_INVALID, "%s: n_vol = %d is not positive", who, (int)n_vol);
+    NCA_REFUSE_NOT_POSITIVE(g_err, who, "n_vol", n_vol);
     if (cyclic != 0 && cyclic != 1) return g_err.fail(NCA_E_INVALID, "%s: cyclic = %d is neither 0 nor 1", who, (int)cyclic);
     if (!(isfinite(eps_s) && eps_s > 0.0)) return g_err.fail(NCA_E_INVALID, "%s: eps_s = %g is not finite and positive", who, eps_s);
     if (!(isfinite(eps_t) && eps_t > 0.0)) return g_err.fail(NCA_E_INVALID, "%s: eps_t = %g is not finite and positive", who, eps_t);

@@ -29,6 +29,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import torch
 
 from . import _capi
+from . import _view
 from . import export as _export
 from . import fused as _fused
 from . import metrics as _metrics
@@ -38,13 +39,6 @@ UNIT_BOUNDS: Bounds = ((-1.0, 1.0),) * 3
 
 
 grid_desc = _capi.grid_desc          # the public name; the leaf module has it so that metrics and phantom need not import this one
-
-
-def _check_volumes(volumes, who):
-    """The volume stack ``who`` (an entry point's name) takes: contiguous float32 [n0,n1,n2] or [n_vol,n0,n1,n2], not empty."""
-    if volumes.dtype != torch.float32 or volumes.dim() not in (3, 4) or not volumes.is_contiguous() or volumes.numel() == 0:
-        raise _capi.NcaError(f"{who} takes contiguous float32 volumes [n0,n1,n2] or [n_vol,n0,n1,n2], got {volumes.dtype} "
-                             f"{tuple(volumes.shape)}{'' if volumes.is_contiguous() else ' (not contiguous)'}")
 
 
 def _default_dists(z: torch.Tensor) -> torch.Tensor:
@@ -57,9 +51,8 @@ def _launch_project(volumes, o, d, z, dists, i0, desc):
     n_vol = 1 if volumes.dim() == 3 else volumes.shape[0]
     R, S = o.shape[0], z.shape[0]
     pix = torch.empty((n_vol, R), dtype=torch.float64, device=volumes.device)
-    with torch.cuda.device(volumes.device):
-        _capi.check_drr(_capi.lib().nca_drr_project(C.byref(desc), _capi.ptr(volumes), n_vol, R, S, _capi.ptr(o), _capi.ptr(d), _capi.ptr(z),
-                                                    _capi.ptr(dists), float(i0), _capi.ptr(pix), _fused._stream()))
+    _view.launch(_capi.check_drr, _capi.lib().nca_drr_project, volumes.device, C.byref(desc), _capi.ptr(volumes), n_vol, R, S, _capi.ptr(o), _capi.ptr(d),
+                 _capi.ptr(z), _capi.ptr(dists), float(i0), _capi.ptr(pix))
     return pix
 
 
@@ -85,9 +78,8 @@ class _ProjectRays(torch.autograd.Function):
         R, S = o.shape[0], z.shape[0]
         g_pix = g_pix.to(torch.float64).contiguous().view(n_vol, R)
         g_vol = torch.zeros((n_vol, math.prod(shape[-3:])), dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _capi.check_drr(_capi.lib().nca_drr_backproject(C.byref(ctx.desc), n_vol, R, S, _capi.ptr(o), _capi.ptr(d), _capi.ptr(z), _capi.ptr(dists),
-                                                            _capi.ptr(g_pix), _capi.ptr(g_vol), _fused._stream()))
+        _view.launch(_capi.check_drr, _capi.lib().nca_drr_backproject, dev, C.byref(ctx.desc), n_vol, R, S, _capi.ptr(o), _capi.ptr(d), _capi.ptr(z),
+                     _capi.ptr(dists), _capi.ptr(g_pix), _capi.ptr(g_vol))
         return g_vol.to(torch.float32).reshape(shape), None, None, None, None, None, None
 
 
@@ -115,7 +107,7 @@ def _project_rays(volumes, origins, dirs, z, dists, i0, bounds, differentiable):
         _fused._require_cuda(dists, "interval lengths")
     if any(t.device != dev for t in (origins, dirs, z) + (() if dists is None else (dists,))):
         raise _capi.NcaError("project_rays: volumes, rays, depths and interval lengths must live on one device")
-    _check_volumes(volumes, "project_rays")
+    _view.check_contiguous_volumes(volumes, "project_rays")
     if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape != dirs.shape or origins.shape[0] == 0:
         raise _capi.NcaError(f"project_rays takes ray origins and directions [R,3], got {tuple(origins.shape)} and {tuple(dirs.shape)}")
     if any(t.dtype not in (torch.float32, torch.float64) for t in (origins, dirs)):
@@ -156,9 +148,8 @@ class _TotalVariation(torch.autograd.Function):
         scale = torch.stack([g_space.to(torch.float64).reshape(()) / float(n_vol * voxels),
                              g_time.to(torch.float64).reshape(()) / float(n_pairs * voxels) if n_pairs else torch.zeros((), dtype=torch.float64, device=dev)])
         g_vol = torch.empty_like(volumes)
-        with torch.cuda.device(dev):
-            _capi.check_vol(_capi.lib().nca_vol_tv_grad(C.byref(desc), _capi.ptr(volumes), n_vol, eps_space, eps_time, int(cyclic), _capi.ptr(scale),
-                                                        _capi.ptr(g_vol), _fused._stream()))
+        _view.launch(_capi.check_vol, _capi.lib().nca_vol_tv_grad, dev, C.byref(desc), _capi.ptr(volumes), n_vol, eps_space, eps_time, int(cyclic),
+                     _capi.ptr(scale), _capi.ptr(g_vol))
         return g_vol, None, None, None, None
 
 
@@ -172,8 +163,7 @@ def _launch_tv(volumes, desc, eps_space, eps_time, cyclic):
     """(tv_space, tv_time) f64 0-d: one nca_vol_tv of checked, contiguous volumes into a zeroed pair, divided by the counts."""
     n_vol, voxels, n_pairs = _tv_counts(volumes, cyclic)
     sums = torch.zeros(2, dtype=torch.float64, device=volumes.device)
-    with torch.cuda.device(volumes.device):
-        _capi.check_vol(_capi.lib().nca_vol_tv(C.byref(desc), _capi.ptr(volumes), n_vol, eps_space, eps_time, int(cyclic), _capi.ptr(sums), _fused._stream()))
+    _view.launch(_capi.check_vol, _capi.lib().nca_vol_tv, volumes.device, C.byref(desc), _capi.ptr(volumes), n_vol, eps_space, eps_time, int(cyclic), _capi.ptr(sums))
     return sums[0] / float(n_vol * voxels), (sums[1] / float(n_pairs * voxels) if n_pairs else torch.zeros((), dtype=torch.float64, device=volumes.device))
 
 
@@ -192,7 +182,7 @@ def total_variation(volumes: torch.Tensor, *, bounds: Bounds, eps_space: float =
     With grad mode on and ``volumes.requires_grad`` both results carry a gradient in ``volumes`` (f32, the volumes' shape, one gathered
     kernel launch, the same bits on every run).  In every other case nothing is recorded."""
     _fused._require_cuda(volumes, "volumes")
-    _check_volumes(volumes, "total_variation")
+    _view.check_contiguous_volumes(volumes, "total_variation")
     eps_space, eps_time = float(eps_space), float(eps_time)
     for eps, what in ((eps_space, "eps_space"), (eps_time, "eps_time")):
         if not (math.isfinite(eps) and eps > 0):

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from . import _view
 from . import fused as _fused
 from .fused import eval_points
 
@@ -137,9 +138,8 @@ def _rays_of(view: "_capi.NcaView", p0: int, n: int, device, dtype):
         raise ValueError("rays are float32 or float64")
     origins = torch.empty((n, 3), dtype=dtype, device=device)
     dirs = torch.empty((n, 3), dtype=dtype, device=device)
-    with torch.cuda.device(origins.device):
-        _capi.check_view(_capi.lib().nca_view_rays(C.byref(view), p0, n, 1 if dtype == torch.float64 else 0, _capi.ptr(origins), _capi.ptr(dirs),
-                                                   _fused._stream()))
+    _view.launch(_capi.check_view, _capi.lib().nca_view_rays, origins.device, C.byref(view), p0, n, 1 if dtype == torch.float64 else 0, _capi.ptr(origins),
+                 _capi.ptr(dirs))
     return origins, dirs
 
 
@@ -168,9 +168,8 @@ def compose_images(pix_s: torch.Tensor, pix_d: Optional[torch.Tensor], i0: float
         raise _capi.NcaError("pix_s and pix_d are both float32 or both float64")
     if any(t.dtype != torch.float32 for t in (pred, pred_s, pred_d)):
         raise _capi.NcaError("the output images are float32")
-    with torch.cuda.device(pix_s.device):
-        _capi.check_view(_capi.lib().nca_view_compose(n, float(i0), _capi.ptr(pix_s), _capi.ptr(pix_d), 1 if pix_s.dtype == torch.float64 else 0,
-                                                      _capi.ptr(pred), _capi.ptr(pred_s), _capi.ptr(pred_d), _fused._stream()))
+    _view.launch(_capi.check_view, _capi.lib().nca_view_compose, pix_s.device, n, float(i0), _capi.ptr(pix_s), _capi.ptr(pix_d),
+                 1 if pix_s.dtype == torch.float64 else 0, _capi.ptr(pred), _capi.ptr(pred_s), _capi.ptr(pred_d))
 
 
 _NORM_IMAGES_PER_CALL = 65535
@@ -189,12 +188,11 @@ def normalize_images(img: torch.Tensor, want_out: bool = True):
     out = torch.empty_like(x) if want_out else None
     minmax = torch.empty((n_img, 2), dtype=torch.float32, device=x.device)
     per = _capi.check_view(lib.nca_image_normalize_workspace(n))
-    with torch.cuda.device(x.device):
-        for i in range(0, n_img, _NORM_IMAGES_PER_CALL):
-            k = min(_NORM_IMAGES_PER_CALL, n_img - i)
-            work = _fused._scratch(per * k, x.device)
-            _capi.check_view(lib.nca_image_normalize(k, n, _capi.ptr(x[i:]), _capi.ptr(out[i:]) if want_out else None, _capi.ptr(minmax[i:]),
-                                                     _capi.ptr(work), per * k, _fused._stream()))
+    for i in range(0, n_img, _NORM_IMAGES_PER_CALL):
+        k = min(_NORM_IMAGES_PER_CALL, n_img - i)
+        work = _fused._scratch(per * k, x.device)
+        _view.launch(_capi.check_view, lib.nca_image_normalize, x.device, k, n, _capi.ptr(x[i:]), _capi.ptr(out[i:]) if want_out else None, _capi.ptr(minmax[i:]),
+                     _capi.ptr(work), per * k)
     return (out.reshape(img.shape) if want_out else None), minmax
 
 
@@ -209,8 +207,7 @@ def _query_points(origins, dirs, z) -> torch.Tensor:
         raise _capi.NcaError("query points are made from float64 rays and float32 depths")
     R, S = origins.shape[0], z.shape[0]
     pts = torch.empty((R * S, 3), dtype=torch.float32, device=origins.device)
-    with torch.cuda.device(origins.device):
-        _capi.check_view(_capi.lib().nca_view_points(R, S, _capi.ptr(origins), _capi.ptr(dirs), _capi.ptr(z), _capi.ptr(pts), _fused._stream()))
+    _view.launch(_capi.check_view, _capi.lib().nca_view_points, origins.device, R, S, _capi.ptr(origins), _capi.ptr(dirs), _capi.ptr(z), _capi.ptr(pts))
     return pts
 
 

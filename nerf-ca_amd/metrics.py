@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from . import _view
 from . import fused as _fused
 
 MAX_WIN = 11          # NCA_SSIM_MAX_WIN
@@ -55,9 +56,8 @@ def _launch_ssim(x, y, rng, win, k1, k2, want_map):
     K = len(win)
     sums = torch.zeros(N, dtype=torch.float64, device=x.device)
     smap = torch.empty((N, H - K + 1, W - K + 1), dtype=torch.float32, device=x.device) if want_map else None
-    with torch.cuda.device(x.device):
-        _capi.check_ssim(_capi.lib().nca_ssim(N, H, W, _capi.ptr(x), _capi.ptr(y), _capi.ptr(rng), K, win, k1, k2, _capi.ptr(sums), _capi.ptr(smap),
-                                              _fused._stream()))
+    _view.launch(_capi.check_ssim, _capi.lib().nca_ssim, x.device, N, H, W, _capi.ptr(x), _capi.ptr(y), _capi.ptr(rng), K, win, k1, k2, _capi.ptr(sums),
+                 _capi.ptr(smap))
     return sums, smap
 
 
@@ -93,10 +93,9 @@ class _Ssim(torch.autograd.Function):
         g_x = torch.empty_like(x)
         lib = _capi.lib()
         nbytes = int(lib.nca_ssim_grad_workspace(N, H, W, K))
-        work = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _capi.check_ssim(lib.nca_ssim_grad(N, H, W, _capi.ptr(x), _capi.ptr(y), _capi.ptr(rng), K, win, k1, k2, _capi.ptr(scale), _capi.ptr(g_x),
-                                               _capi.ptr(work), nbytes, _fused._stream()))
+        work = _view.workspace(nbytes, dev)
+        _view.launch(_capi.check_ssim, lib.nca_ssim_grad, dev, N, H, W, _capi.ptr(x), _capi.ptr(y), _capi.ptr(rng), K, win, k1, k2, _capi.ptr(scale), _capi.ptr(g_x),
+                     _capi.ptr(work), nbytes)
         return g_x, None, None, None, None, None, None
 
 
@@ -200,16 +199,6 @@ def compare_sequences(pred: dict, truth: dict, *, data_range: Optional[Union[flo
 MAX_AXIS = 512          # NCA_EDT_MAX_AXIS
 
 
-def _check_volume(vol, who, what="vol"):
-    if not isinstance(vol, torch.Tensor):
-        raise _capi.NcaError(f"{who}: {what} is not a tensor")
-    _fused._require_cuda(vol, what)
-    if vol.dtype != torch.float32:
-        raise _capi.NcaError(f"{who} takes float32 volumes, got {vol.dtype}")
-    if vol.dim() < 3 or vol.numel() == 0:
-        raise _capi.NcaError(f"{who} takes a stack [..., n0, n1, n2], got {tuple(vol.shape)}")
-
-
 @torch.no_grad()
 def distance_transform(vol: torch.Tensor, bounds, *, threshold: float, inside: bool = False) -> torch.Tensor:
     """The exact Euclidean distance transform of a thresholded f32 stack ``vol`` ``[..., n0, n1, n2]`` on the device, as an f32 tensor of
@@ -221,21 +210,14 @@ def distance_transform(vol: torch.Tensor, bounds, *, threshold: float, inside: b
 
     One ``nca_vol_edt`` (three launches; its definition, operation by operation, is in include/nerfca_hip.h, "edt"): the same bits on
     every run.  Not differentiable: it runs under ``no_grad`` and the result is detached.  An axis longer than 512 nodes is refused."""
-    _check_volume(vol, "distance_transform")
-    threshold = float(threshold)
-    if math.isnan(threshold):
-        raise _capi.NcaError("distance_transform: threshold = nan is not a number")
-    shape = tuple(vol.shape[-3:])
-    desc = _capi.grid_desc(shape, bounds)
-    x = vol.detach().reshape((-1,) + shape).contiguous()
-    n_vol = x.shape[0]
+    _view.check_volume(vol, "distance_transform")          # refused before the threshold is looked at
+    threshold = _view.finite_threshold(threshold, "distance_transform")
+    desc, x, n_vol, _ = _view.volume_stack(vol, "distance_transform", bounds)
     out = torch.empty_like(x)
     lib = _capi.lib()
     nbytes = int(lib.nca_vol_edt_workspace(C.byref(desc), n_vol))
-    work = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=x.device)
-    with torch.cuda.device(x.device):
-        _capi.check_edt(lib.nca_vol_edt(C.byref(desc), _capi.ptr(x), n_vol, threshold, 1 if inside else 0, _capi.ptr(out), _capi.ptr(work), nbytes,
-                                        _fused._stream()))
+    work = _view.workspace(nbytes, x.device)
+    _view.launch(_capi.check_edt, lib.nca_vol_edt, x.device, C.byref(desc), _capi.ptr(x), n_vol, threshold, 1 if inside else 0, _capi.ptr(out), _capi.ptr(work), nbytes)
     return out.reshape(vol.shape)
 
 
@@ -296,8 +278,8 @@ def mask_distances(pred: torch.Tensor, truth: torch.Tensor, bounds, *, threshold
 
     Two ``distance_transform`` calls (and, with ``surface``, two ``ccta.mask_border``); the reductions are torch on the device.  An entry
     whose A or B is empty is NaN in every distance (its counts are still returned); identical masks give exactly 0 in every distance."""
-    _check_volume(pred, "mask_distances", "pred")
-    _check_volume(truth, "mask_distances", "truth")
+    _view.check_volume(pred, "mask_distances", "pred")
+    _view.check_volume(truth, "mask_distances", "truth")
     if pred.shape != truth.shape:
         raise _capi.NcaError(f"mask_distances takes two stacks of one shape, got {tuple(pred.shape)} and {tuple(truth.shape)}")
     if pred.device != truth.device:
@@ -367,7 +349,7 @@ def centreline_coverage(vol: torch.Tensor, bounds, points, *, threshold: float, 
     The nearest-node read adds at most half a cell diagonal to a point's true distance from the mask (the node is at most that far from
     the point), so a ``tol`` of one cell diagonal accepts centreline points up to one and a half diagonals away and never rejects one
     within half a diagonal."""
-    _check_volume(vol, "centreline_coverage")
+    _view.check_volume(vol, "centreline_coverage")
     if vol.dim() not in (3, 4):
         raise _capi.NcaError(f"centreline_coverage takes [P, n0, n1, n2] or [n0, n1, n2], got {tuple(vol.shape)}")
     return coverage_reductions(distance_transform(vol, bounds, threshold=float(threshold)), bounds, points, tol)

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from . import fused as _fused
+from . import _view
 
 SEG_BATCH = 512          # NCA_PHANTOM_SEG_BATCH: the segments staged through LDS at once
 
@@ -205,9 +205,8 @@ def voxelize(shape: Sequence[int], bounds, *, ellipsoids=None, segments=None, rh
 
     d_ell, d_seg = upload(ell, n_ell), upload(seg, n_seg)
     out = torch.empty((P,) + shape, dtype=torch.float32, device=dev)
-    with torch.cuda.device(out.device):
-        _capi.check_phantom(_capi.lib().nca_phantom_voxelize(C.byref(desc), P, n_ell, _capi.ptr(d_ell), n_seg, _capi.ptr(d_seg), rho_vessel, edge,
-                                                             _capi.ptr(out), _fused._stream()))
+    _view.launch(_capi.check_phantom, _capi.lib().nca_phantom_voxelize, out.device, C.byref(desc), P, n_ell, _capi.ptr(d_ell), n_seg, _capi.ptr(d_seg), rho_vessel,
+                 edge, _capi.ptr(out))
     return out
 
 

@@ -108,12 +108,6 @@ def case(shape, pattern, inv, invert=0):
     return vol, want
 
 
-def ulp_distance(a, b):
-    """Whole f32 steps between two f32 arrays of non-negative values (inf equals inf)."""
-    a, b = np.asarray(a, dtype=np.float32), np.asarray(b, dtype=np.float32)
-    return np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))
-
-
 def directed(dist, mask, percentile):
     """(count, sum, max, quantile "higher") of f64 `dist` over `mask`, in numpy."""
     d = np.sort(np.asarray(dist, dtype=np.float64)[mask])

@@ -4,8 +4,9 @@ the scalar every render-parity test differentiates,
     sum(pix * cp) + 50 sum(sigma_s * cs) + 50 sum(sigma_d * cd),
 
 launch counting, the bf16 bounds, the per-entry gradient checks on one-hot upstream gradients (nets with decided ReLU masks, the rank-one
-split, `scaled_err`, the ray and point cases with their memoised oracle gradients), and what the launch-free tests of the view sections (csrc/view/) share: the `capi` / `lib` fixtures, the
-declared-bound-exported check, `refused` and the one list of NcaGrid refusals.  Test modules import from here (and from conftest.py), never from one another.  Every helper
+split, `scaled_err`, the ray and point cases with their memoised oracle gradients), what the launch-free tests of the view sections (csrc/view/) share: the `capi` / `lib` fixtures, the
+declared-bound-exported check, `refused` and the one list of NcaGrid refusals, and what their GPU tests share: `grid_of`, `same_bits`, `ulp_distance` and the raw launch of a
+workspace-taking entry point, `gpu_stack_call`.  Test modules import from here (and from conftest.py), never from one another.  Every helper
 draws from the generator it is given in a fixed, documented order: the tolerances of the tests were measured on those draws.
 """
 import contextlib
@@ -17,6 +18,7 @@ import os
 import re
 import socket
 
+import numpy as np
 import pytest
 import torch
 
@@ -562,3 +564,41 @@ def grid_refusals(section, capi, lib, call):
     big = (1 << 31) - 1
     no(grid(capi, n=(big, big, big)), "overflow", str(big))
     no(grid(capi, n=(1 << 20, 1 << 20, 1 << 20)), "overflow", str(1 << 20), count=4)          # 2^60 voxels x 4 x at least 4 bytes
+
+
+# ------------------------------------------------------------------------------------------ the view sections on the GPU
+def grid_of(shape, inv=(1.0, 2.0, 0.5)):
+    """The NcaGrid of the raw launches: a lo that is not 0 and, unless given, a spacing of its own on every axis."""
+    from nerfca_amd import _capi
+    return grid(_capi, n=shape, lo=(0.0, -1.0, 2.0), inv=inv)
+
+
+def same_bits(got, want):
+    """Two f32 numpy arrays of one shape with the same bits (NaN payloads and the sign of zero included)."""
+    return got.shape == want.shape and got.dtype == want.dtype == np.float32 and np.array_equal(got.view(np.int32), want.view(np.int32))
+
+
+def ulp_distance(got, want):
+    """Whole steps of their format between two f32 or two f64 numpy arrays, entry by entry (as f64; between values of one sign, inf equals inf)."""
+    assert got.dtype == want.dtype, (got.dtype, want.dtype)
+    kind = {4: np.int32, 8: np.int64}[want.dtype.itemsize]
+    return np.abs(got.view(kind).astype(np.float64) - want.view(kind).astype(np.float64))
+
+
+def gpu_stack_call(dev, check, fn, query, g, vol, args, fill, dtype, node_bytes, out_shape=None, query_args=()):
+    """The output (numpy) of one raw call `fn(g, vol, n_vol, *args, out, work, work_bytes, stream)` on the f32 stack `vol` [n_vol,n0,n1,n2]: `out`
+    (of `dtype`, the stack's shape unless given) is pre-filled with `fill`, so a node the kernels did not write shows; the workspace is exactly as
+    large as `query(g, n_vol, *query_args)` says -- at least `node_bytes` per node in whole 256-byte lines, none at all when `node_bytes` is 0 --
+    and pre-filled with 0xff bytes."""
+    from nerfca_amd import _capi, fused
+    vol = np.ascontiguousarray(vol, dtype=np.float32)
+    n_vol = vol.shape[0]
+    x = torch.tensor(vol).to(dev)
+    out = torch.full(vol.shape if out_shape is None else out_shape, fill, dtype=dtype, device=dev)
+    nbytes = query(C.byref(g), n_vol, *query_args)
+    assert (nbytes >= node_bytes * vol.size and nbytes % 256 == 0) if node_bytes else nbytes == 0
+    work = torch.full((nbytes,), 0xff, dtype=torch.uint8, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        check(fn(C.byref(g), _capi.ptr(x), n_vol, *args, _capi.ptr(out), _capi.ptr(work), nbytes, fused._stream()))
+    torch.cuda.synchronize(dev)
+    return out.cpu().numpy()

@@ -36,8 +36,7 @@ def test_new_names_are_declared_bound_and_exported(capi):
     assert nerfca_amd.metrics.mask_distances and nerfca_amd.metrics.centreline_coverage and nerfca_amd.phantom.centreline_points
 
 
-def grid(capi, n=(4, 5, 6), lo=(0.0, 0.0, 0.0), inv=(1.0, 2.0, 3.0), reserved=0):
-    return T.grid(capi, n, lo, inv, reserved)
+grid = functools.partial(T.grid, n=(4, 5, 6), lo=(0.0, 0.0, 0.0), inv=(1.0, 2.0, 3.0))
 
 
 def test_refusals(capi, lib):
@@ -129,7 +128,7 @@ def test_oracle_against_scipy(shape):
                 got = np.sqrt(q).astype(np.float32)
                 assert np.array_equal(got, ref.edt(vol, inv, ref.THRESHOLD, invert))
                 sci = scipy.ndimage.distance_transform_edt(~feat, sampling=ref.spacing(inv))
-                steps = int(ref.ulp_distance(got, sci.astype(np.float32)).max())
+                steps = int(T.ulp_distance(got, sci.astype(np.float32)).max())
                 assert steps <= (0 if inv == ref.UNIT else 1), (shape, pattern, invert, inv, steps)
                 if q.max() > 0:
                     with np.errstate(invalid="ignore", divide="ignore"):

@@ -6,7 +6,6 @@ Tile sizes of the kernels: the row pass takes one wave per row and chunks of 64 
 columns and 16 nodes along the line per step.  Shapes: (2,2,2); (3,5,64) one chunk; (3,5,65) one node past it; (5,9,130) two chunk carries;
 (3,17,18) one past the 16 nodes of a step along axis 1 and one column tile past 16; (17,3,6) the same along axis 0 (its columns are the 18
 nodes of a plane); (512,2,2) the longest line, the whole 64 KiB of LDS."""
-import ctypes as C
 import math
 
 import numpy as np
@@ -14,39 +13,20 @@ import pytest
 import scipy.ndimage
 import torch
 
-from nca_testlib import dev  # noqa: F401
+from nca_testlib import dev, grid_of, gpu_stack_call, same_bits, ulp_distance  # noqa: F401
 
 import edt_ref as ref
 
 pytestmark = pytest.mark.gpu
 
 
-def grid_of(shape, inv):
-    from nerfca_amd import _capi
-    return _capi.NcaGrid(lo=(C.c_double * 3)(0.0, -1.0, 2.0), inv=(C.c_double * 3)(*inv), n=(C.c_int32 * 3)(*shape), reserved=0)
-
-
 def gpu_edt(dev, vol, inv, threshold=ref.THRESHOLD, invert=0):
     """out f32 of one nca_vol_edt of a stack [n_vol,n0,n1,n2] into a buffer pre-filled with NaN, the workspace exactly as large as the query says
     (and itself pre-filled, with 0xff bytes)."""
-    from nerfca_amd import _capi, fused
+    from nerfca_amd import _capi
     lib = _capi.lib()
-    vol = np.ascontiguousarray(vol, dtype=np.float32)
-    n_vol, shape = vol.shape[0], vol.shape[1:]
-    g = grid_of(shape, inv)
-    x = torch.tensor(vol).to(dev)
-    out = torch.full(vol.shape, math.nan, dtype=torch.float32, device=dev)
-    nbytes = lib.nca_vol_edt_workspace(C.byref(g), n_vol)
-    assert nbytes >= 12 * vol.size and nbytes % 256 == 0
-    work = torch.full((nbytes,), 0xff, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check_edt(lib.nca_vol_edt(C.byref(g), _capi.ptr(x), n_vol, float(threshold), invert, _capi.ptr(out), _capi.ptr(work), nbytes, fused._stream()))
-    torch.cuda.synchronize(dev)
-    return out.cpu().numpy()
-
-
-def same_bits(got, want):
-    return got.shape == want.shape and np.array_equal(got.view(np.int32), want.view(np.int32))
+    return gpu_stack_call(dev, _capi.check_edt, lib.nca_vol_edt, lib.nca_vol_edt_workspace, grid_of(np.shape(vol)[1:], inv), vol, (float(threshold), invert), math.nan,
+                          torch.float32, 12)
 
 
 @pytest.mark.parametrize("inv", [ref.UNIT, ref.ANISO], ids=["unit", "aniso"])
@@ -60,7 +40,7 @@ def test_every_pattern_bit_for_bit(dev, shape, inv):
     got = gpu_edt(dev, vols, inv)
     for k, p in enumerate(ref.PATTERNS):
         assert not np.isnan(got[k]).any(), p
-        assert same_bits(got[k], want[k]), (p, int(ref.ulp_distance(got[k], want[k]).max()))
+        assert same_bits(got[k], want[k]), (p, int(ulp_distance(got[k], want[k]).max()))
     assert same_bits(gpu_edt(dev, vols, inv), got)
     for k in (0, ref.PATTERNS.index("d0.05"), ref.PATTERNS.index("none")):
         assert same_bits(gpu_edt(dev, vols[k:k + 1], inv)[0], got[k]), ref.PATTERNS[k]
@@ -144,7 +124,7 @@ def test_distance_transform_against_scipy(dev):
         for k in range(2):
             mask = vol[k] > ref.THRESHOLD
             sci = scipy.ndimage.distance_transform_edt(mask if inside else ~mask, sampling=h).astype(np.float32)
-            assert int(ref.ulp_distance(got[k].cpu().numpy(), sci).max()) <= 1, (inside, k)
+            assert int(ulp_distance(got[k].cpu().numpy(), sci).max()) <= 1, (inside, k)
     unit = metrics.distance_transform(x[0], ((0.0, 4.0), (0.0, 8.0), (0.0, 129.0)), threshold=ref.THRESHOLD, inside=True)
     assert same_bits(unit.cpu().numpy(), scipy.ndimage.distance_transform_edt(vol[0] > ref.THRESHOLD).astype(np.float32))
     lead = metrics.distance_transform(x.reshape((2, 1) + shape), BOUNDS, threshold=ref.THRESHOLD)

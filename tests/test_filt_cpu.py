@@ -43,8 +43,7 @@ def test_new_names_are_declared_bound_and_exported(capi):
         assert callable(getattr(ccta, name)), name
 
 
-def grid(capi, n=(4, 5, 6), lo=(0.0, 0.0, 0.0), inv=(1.0, 2.0, 3.0), reserved=0):
-    return T.grid(capi, n, lo, inv, reserved)
+grid = functools.partial(T.grid, n=(4, 5, 6), lo=(0.0, 0.0, 0.0), inv=(1.0, 2.0, 3.0))
 
 
 def c_radius(r):

@@ -16,59 +16,30 @@ import pytest
 import scipy.ndimage
 import torch
 
-from nca_testlib import dev  # noqa: F401
+from nca_testlib import dev, grid_of, gpu_stack_call, same_bits  # noqa: F401
 
 import filt_ref as ref
 
 pytestmark = pytest.mark.gpu
 
 
-def grid_of(shape):
-    from nerfca_amd import _capi
-    return _capi.NcaGrid(lo=(C.c_double * 3)(0.0, -1.0, 2.0), inv=(C.c_double * 3)(1.0, 2.0, 0.5), n=(C.c_int32 * 3)(*shape), reserved=0)
-
-
 def gpu_smooth(dev, vol, sigma, radius):
     """out f32 of one nca_vol_smooth of a stack [n_vol,n0,n1,n2] into a buffer pre-filled with NaN, the workspace exactly as large as the
     query says (and itself pre-filled, with 0xff bytes)."""
-    from nerfca_amd import _capi, ccta, fused
+    from nerfca_amd import _capi, ccta
     lib = _capi.lib()
-    vol = np.ascontiguousarray(vol, dtype=np.float32)
-    n_vol, shape = vol.shape[0], vol.shape[1:]
-    g = grid_of(shape)
     halves = [ccta.gaussian_weights(float(s), int(r)) for s, r in zip(ref.per_axis(sigma), ref.per_axis(radius))]
     flat = np.concatenate(halves)
-    x = torch.tensor(vol).to(dev)
-    out = torch.full(vol.shape, math.nan, dtype=torch.float32, device=dev)
-    nbytes = lib.nca_vol_smooth_workspace(C.byref(g), n_vol)
-    assert nbytes >= 16 * vol.size and nbytes % 256 == 0
-    work = torch.full((nbytes,), 0xff, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check_filt(lib.nca_vol_smooth(C.byref(g), _capi.ptr(x), n_vol, (C.c_int32 * 3)(*[len(h) - 1 for h in halves]), (C.c_double * flat.size)(*flat.tolist()),
-                                            _capi.ptr(out), _capi.ptr(work), nbytes, fused._stream()))
-    torch.cuda.synchronize(dev)
-    return out.cpu().numpy()
+    args = ((C.c_int32 * 3)(*[len(h) - 1 for h in halves]), (C.c_double * flat.size)(*flat.tolist()))
+    return gpu_stack_call(dev, _capi.check_filt, lib.nca_vol_smooth, lib.nca_vol_smooth_workspace, grid_of(np.shape(vol)[1:]), vol, args, math.nan, torch.float32, 16)
 
 
 def gpu_cityblock(dev, vol, threshold=0.5, invert=0, border=0):
-    from nerfca_amd import _capi, fused
+    """out int32 of one nca_vol_cityblock, likewise, into a buffer pre-filled with -1."""
+    from nerfca_amd import _capi
     lib = _capi.lib()
-    vol = np.ascontiguousarray(vol, dtype=np.float32)
-    n_vol, shape = vol.shape[0], vol.shape[1:]
-    g = grid_of(shape)
-    x = torch.tensor(vol).to(dev)
-    out = torch.full(vol.shape, -1, dtype=torch.int32, device=dev)
-    nbytes = lib.nca_vol_cityblock_workspace(C.byref(g), n_vol)
-    assert nbytes >= 8 * vol.size and nbytes % 256 == 0
-    work = torch.full((nbytes,), 0xff, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _capi.check_filt(lib.nca_vol_cityblock(C.byref(g), _capi.ptr(x), n_vol, float(threshold), invert, border, _capi.ptr(out), _capi.ptr(work), nbytes, fused._stream()))
-    torch.cuda.synchronize(dev)
-    return out.cpu().numpy()
-
-
-def same_bits(got, want):
-    return got.shape == want.shape and got.dtype == want.dtype == np.float32 and np.array_equal(got.view(np.int32), want.view(np.int32))
+    return gpu_stack_call(dev, _capi.check_filt, lib.nca_vol_cityblock, lib.nca_vol_cityblock_workspace, grid_of(np.shape(vol)[1:]), vol,
+                          (float(threshold), invert, border), -1, torch.int32, 8)
 
 
 # ----------------------------------------------------------------------------- smoothing

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from nca_testlib import dev  # noqa: F401
+from nca_testlib import dev, same_bits  # noqa: F401
 
 import phantom_ref as ref
 
@@ -61,10 +61,6 @@ def gpu_voxelize(dev, shape, ell, seg, rho_v, edge, cull, bounds=BOUNDS):
         return out.cpu().numpy()
     finally:
         _capi.check_phantom(lib.nca_phantom_set_cull(old))
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def check(got, want64, mass, edge, bounds=BOUNDS):

@@ -38,8 +38,7 @@ def test_new_names_are_declared_bound_and_exported(capi):
         assert callable(getattr(ccta, name)), name
 
 
-def grid(capi, n=(4, 5, 6), lo=(0.0, 0.0, 0.0), inv=(1.0, 2.0, 3.0), reserved=0):
-    return T.grid(capi, n, lo, inv, reserved)
+grid = functools.partial(T.grid, n=(4, 5, 6), lo=(0.0, 0.0, 0.0), inv=(1.0, 2.0, 3.0))
 
 
 def c_m(m):
@@ -242,7 +241,7 @@ def test_prepare_ccta_without_resample_takes_the_old_path(monkeypatch):
     from nerfca_amd import ccta
     calls, seen = [], {}
     monkeypatch.setattr(ccta, "zoom", lambda *a, **k: calls.append((a, k)) or (_ for _ in ()).throw(AssertionError("zoom was called")))
-    monkeypatch.setattr(ccta._metrics, "_check_volume", lambda *a, **k: None)
+    monkeypatch.setattr(ccta._view, "check_volume", lambda *a, **k: None)
     monkeypatch.setattr(ccta, "_mask_input", lambda vol, who: vol)
 
     def contrast(m, bounds, **kw):

@@ -15,17 +15,12 @@ import pytest
 import scipy.ndimage
 import torch
 
-from nca_testlib import dev  # noqa: F401
+from nca_testlib import dev, grid_of, gpu_stack_call, same_bits, ulp_distance  # noqa: F401
 
 import filt_ref
 import resample_ref as ref
 
 pytestmark = pytest.mark.gpu
-
-
-def grid_of(shape):
-    from nerfca_amd import _capi
-    return _capi.NcaGrid(lo=(C.c_double * 3)(0.0, -1.0, 2.0), inv=(C.c_double * 3)(1.0, 2.0, 0.5), n=(C.c_int32 * 3)(*shape), reserved=0)
 
 
 def gpu_filter(dev, vol):
@@ -45,30 +40,19 @@ def gpu_filter(dev, vol):
 def gpu_zoom(dev, vol, m, order):
     """out f32 of one nca_vol_zoom of a stack into a buffer pre-filled with NaN (order 3) or with 12345 (order 0, which may carry a NaN), the
     workspace exactly as large as the query says and pre-filled with 0xff bytes; none at all at order 0."""
-    from nerfca_amd import _capi, fused
+    from nerfca_amd import _capi
     lib = _capi.lib()
-    vol = np.ascontiguousarray(vol, dtype=np.float32)
-    n_vol = vol.shape[0]
-    g = grid_of(vol.shape[1:])
-    x = torch.tensor(vol).to(dev)
-    out = torch.full((n_vol,) + tuple(m), math.nan if order == 3 else 12345.0, dtype=torch.float32, device=dev)
-    nbytes = lib.nca_vol_zoom_workspace(C.byref(g), n_vol, order)
-    assert (nbytes >= 8 * vol.size and nbytes % 256 == 0) if order == 3 else nbytes == 0
-    work = torch.full((nbytes,), 0xff, dtype=torch.uint8, device=dev) if nbytes else None
-    with torch.cuda.device(dev):
-        _capi.check_resample(lib.nca_vol_zoom(C.byref(g), _capi.ptr(x), n_vol, (C.c_int32 * 3)(*m), order, _capi.ptr(out), _capi.ptr(work), nbytes, fused._stream()))
-    torch.cuda.synchronize(dev)
-    return out.cpu().numpy()
+    return gpu_stack_call(dev, _capi.check_resample, lib.nca_vol_zoom, lib.nca_vol_zoom_workspace, grid_of(np.shape(vol)[1:]), vol, ((C.c_int32 * 3)(*m), order),
+                          math.nan if order == 3 else 12345.0, torch.float32, 8 if order == 3 else 0, out_shape=(np.shape(vol)[0],) + tuple(m), query_args=(order,))
 
 
-def same_bits(got, want):
-    kind = {4: np.int32, 8: np.int64}[want.dtype.itemsize]
-    return got.shape == want.shape and got.dtype == want.dtype and np.array_equal(got.view(kind), want.view(kind))
+def same_bits64(got, want):
+    """nca_testlib.same_bits for the f64 coefficients."""
+    return got.shape == want.shape and got.dtype == want.dtype == np.float64 and np.array_equal(got.view(np.int64), want.view(np.int64))
 
 
 def ulps(got, want):
-    kind = {4: np.int32, 8: np.int64}[want.dtype.itemsize]
-    return int(np.abs(got.view(kind).astype(np.float64) - want.view(kind).astype(np.float64)).max())
+    return int(ulp_distance(got, want).max())
 
 
 # (shape, output shape): factors above 1, below 1 and exactly 1 on different axes of one call wherever the shape allows
@@ -84,8 +68,8 @@ def test_filter_and_zoom_bit_for_bit(dev, shape, m):
     want_c = ref.spline_filter(stack)
     got_c = gpu_filter(dev, stack)
     assert not np.isnan(got_c).any()
-    assert same_bits(got_c, want_c), ulps(got_c, want_c)
-    assert same_bits(gpu_filter(dev, stack), got_c)
+    assert same_bits64(got_c, want_c), ulps(got_c, want_c)
+    assert same_bits64(gpu_filter(dev, stack), got_c)
     for order in (3, 0):
         want = ref.zoom(stack, m, order)
         got = gpu_zoom(dev, stack, m, order)
@@ -95,7 +79,7 @@ def test_filter_and_zoom_bit_for_bit(dev, shape, m):
         for k in range(3):
             assert same_bits(gpu_zoom(dev, stack[k:k + 1], m, order)[0], got[k]), (order, k)
     for k in range(3):
-        assert same_bits(gpu_filter(dev, stack[k:k + 1])[0], got_c[k]), k
+        assert same_bits64(gpu_filter(dev, stack[k:k + 1])[0], got_c[k]), k
     if shape == (4, 3, 3):
         assert ref.overshoots(4, 188) and same_bits(gpu_zoom(dev, stack, m, 0)[:, -1], stack[:, -1])
 
@@ -110,7 +94,7 @@ def test_the_longest_axis(dev):
         m[axis] = 300
         stack = np.stack([ref.volume(tuple(shape), seed=s) for s in range(2)])
         got_c = gpu_filter(dev, stack)
-        assert same_bits(got_c, ref.spline_filter(stack)), (axis, ulps(got_c, ref.spline_filter(stack)))
+        assert same_bits64(got_c, ref.spline_filter(stack)), (axis, ulps(got_c, ref.spline_filter(stack)))
         got = gpu_zoom(dev, stack, m, 3)
         assert same_bits(got, ref.zoom(stack, m, 3)), axis
         shape[axis] = 513
