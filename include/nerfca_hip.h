@@ -904,6 +904,59 @@ int nca_vol_zoom(const NcaGrid* grid_in, const float* vol, int32_t n_vol, const 
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_resample_last_error(void);
 
+/* ---- skel: the soft skeleton of voxel stacks and the sums clDice is made of (metrics.soft_skeleton / cldice) -------------------------------
+ * The soft skeleton of Shit et al., "clDice -- a novel topology-preserving loss function for tubular structure segmentation" (CVPR 2021),
+ * built from minimum and maximum stencils only, so it is exact in f32 and has the same bits on every run; and the two sums per volume from
+ * which the topology precision and sensitivity of clDice follow.  Purely additive to ABI 13.  Like the other view sections these entry
+ * points keep their OWN per-thread message (the accessor below); a refused call launches nothing and reads no device pointer; a launch
+ * failure is reported once.  vol is f32 [n_vol][n0][n1][n2] contiguous on the device, on one NcaGrid (`grid` is a host pointer; lo and inv
+ * are validated but unused: the stencils count in nodes).  Every volume is treated on its own: its result does not depend on n_vol or on
+ * its neighbours in the stack.
+ *
+ * SOFT SKELETON.  Neighbours outside the grid are LEFT OUT (the -inf padding of max_pool3d; not the border_value = 0 of
+ * ccta.binary_erosion: a volume that is 1 everywhere has an empty skeleton).
+ *     min(a, b) = (b < a) ? b : a;   max(a, b) = (b > a) ? b : a;   relu(x) = (x > 0) ? x : +0
+ *     erode(x)[i]  = the minimum over node i and its up to six axis neighbours: a = x[i], then a = min(a, x[i + o]) for the offsets
+ *                    o = (-1,0,0), (0,-1,0), (0,0,-1), (0,0,+1), (0,+1,0), (+1,0,0) that stay inside the grid, in this (raster) order;
+ *     dilate(x)[i] = the maximum over the up to 27 nodes of the 3 x 3 x 3 box around i: a = x[i], then a = max(a, x[i + o]) for the 26
+ *                    offsets o != 0 in raster order, (-1,-1,-1), (-1,-1,0), .., (+1,+1,+1), that stay inside the grid;
+ *     open(x) = dilate(erode(x)).
+ * The order matters only for a NaN and for the sign of a zero: a NaN at the centre stays, a NaN neighbour is passed over; filling the
+ * nodes outside the grid with +inf (erode) and -inf (dilate) is equivalent.  With iterations = K:
+ *     E_0 = vol;   S = relu(E_0 - open(E_0));
+ *     for j = 1 .. K:   E_j = erode(E_{j-1});   d = relu(E_j - open(E_j));   S = S + relu(d - S * d);
+ *     out = S.
+ * Every operation is ONE rounded f32 operation in the order written (no fused multiply-add).  For finite input the result equals, as
+ * values, the published torch expression with soft_erode = the minimum of three 1-D -max_pool3d(-x) and soft_dilate = max_pool3d(x, 3, 1,
+ * 1).  For a binary volume the result is binary and a subset of the volume.
+ * K + 1 launches of one kernel: launch j stages a tile of E_j with a halo of two nodes in LDS, forms E_{j+1} on the tile grown by one
+ * node, its box maximum, d and the update of S, and writes E_{j+1} and S for the tile's own nodes.  S lives in `out` and is updated in
+ * place; the first launch writes every node of it.  E_j and E_{j+1} are the workspace: 8 bytes per node, rounded up to a multiple of 256.
+ * The query returns it, and 0 for arguments the entry point refuses.  No atomics: the same bits on every run.  The tiling sets no limit on an
+ * axis.  out may NOT alias vol (out == vol is refused; an overlap is not detected).
+ * NCA_E_INVALID (the message names the value): a NULL grid, vol or out; out == vol; n_vol <= 0; the grid refusals of nca_drr_project;
+ * iterations < 0; more than 2^31 - 1 tiles of 4 x 8 x 64 nodes in the stack (what one launch covers).  NCA_E_UNSUPPORTED: iterations above
+ * NCA_SKEL_MAX_ITER.  NCA_E_WORKSPACE: work is NULL or work_bytes is below the query's answer. */
+enum { NCA_SKEL_MAX_ITER = 512 };
+size_t nca_vol_softskel_workspace(const NcaGrid* grid, int32_t n_vol);
+int nca_vol_softskel(const NcaGrid* grid, const float* vol, int32_t n_vol, int32_t iterations, float* out, void* work, size_t work_bytes, void* stream);
+
+/* OVERLAP SUMS.  a, b f32 [n_vol][n0][n1][n2] on the device (they may be the same stack); sums f64 [n_vol][2] on the device:
+ *     sums[2 v] = the sum over the nodes i of volume v of (double)a[i] * (double)b[i];     sums[2 v + 1] = the sum of (double)a[i].
+ * Each product is exact in f64.  The order of addition is fixed: a workgroup of 256 threads owns 4096 consecutive nodes of one volume,
+ * thread t adds the nodes t, t + 256, .. in this order and the workgroup adds its threads in a binary tree; the per-workgroup sums are the
+ * workspace (16 bytes per 4096 nodes of a volume, rounded up to a multiple of 256), and a second launch adds them per volume the same way.
+ * No atomics: the same bits on every run.  Against the exact sum the result is within N 2^-53 of the sum of the absolute terms, N the
+ * nodes of a volume; sums of whole numbers below 2^53 are exact.
+ * NCA_E_INVALID: a NULL grid, a, b or sums; n_vol <= 0; the grid refusals of nca_drr_project; more than 2^24 workgroups in the first
+ * launch.  NCA_E_WORKSPACE: work is NULL or work_bytes is below the query's answer.  The query returns 0 for arguments the entry point
+ * refuses. */
+size_t nca_vol_overlap_sums_workspace(const NcaGrid* grid, int32_t n_vol);
+int nca_vol_overlap_sums(const NcaGrid* grid, const float* a, const float* b, int32_t n_vol, double* sums, void* work, size_t work_bytes, void* stream);
+
+/* The message of the calling thread's last failed call of this section. */
+const char* nca_skel_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,9 @@ the first is the prediction, the second the truth.  For every file both hold: ph
 > threshold) and metrics.mask_distances (mean, Hausdorff and percentile distances between the masks, in the world units of --bounds, per
 volume of the stack).  --pred-threshold thresholds the prediction at a value of its own (a sparse-view fit rarely reaches the truth's
 densities); --pred-fraction F sets it to F times the prediction's own maximum instead.  --surface measures between the borders of the two
-masks (metrics.mask_distances(surface=True)) and marks the record with "surface": true.  Prints one JSON record, and writes it with --out.
+masks (metrics.mask_distances(surface=True)) and marks the record with "surface": true.  --cldice K adds the centreline Dice of the two
+masks (metrics.cldice at K iterations, the same thresholds) per volume: "cldice", "tprec", "tsens" and "cldice_iterations".  Prints one JSON
+record, and writes it with --out.
 """
 import argparse
 import json
@@ -45,12 +47,13 @@ def parser():
     ap.add_argument("--pred-fraction", type=float, default=None, help="threshold the prediction at this fraction of its own maximum")
     ap.add_argument("--percentile", type=float, default=95.0)
     ap.add_argument("--surface", action="store_true", help="measure between the borders of the masks (MedPy's surface distances), not between whole bodies")
+    ap.add_argument("--cldice", type=int, default=None, metavar="K", help="add clDice, topology precision and sensitivity of the masks at K skeleton iterations")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--out", default=None, help="also write the record to this file")
     return ap
 
 
-def compare(pred, truth, bounds, threshold, pred_threshold, percentile, surface=False):
+def compare(pred, truth, bounds, threshold, pred_threshold, percentile, surface=False, cldice=None):
     """The record of one pair of device tensors of one shape."""
     from nerfca_amd import metrics, phantom
     rec = phantom.volume_errors(pred, truth, threshold)
@@ -59,6 +62,9 @@ def compare(pred, truth, bounds, threshold, pred_threshold, percentile, surface=
         rec["surface"] = True
     dist = metrics.mask_distances(pred, truth, bounds, threshold=threshold, pred_threshold=pred_threshold, percentile=percentile, surface=surface)
     rec.update({k: v.reshape(-1).tolist() for k, v in dist.items()})
+    if cldice is not None:
+        rec["cldice_iterations"] = cldice
+        rec.update({k: v.reshape(-1).tolist() for k, v in metrics.cldice(pred, truth, iterations=cldice, threshold=threshold, pred_threshold=pred_threshold).items()})
     return rec
 
 
@@ -76,7 +82,7 @@ def main(argv=None):
         if pred.shape != truth.shape:
             sys.exit(f"compare_volumes: {a} is {tuple(pred.shape)}, {b} is {tuple(truth.shape)}")
         pthr = args.pred_threshold if args.pred_fraction is None else args.pred_fraction * float(pred.max())
-        out[name] = compare(pred, truth, args.bounds, args.threshold, pthr, args.percentile, args.surface)
+        out[name] = compare(pred, truth, args.bounds, args.threshold, pthr, args.percentile, args.surface, args.cldice)
     if not any(n in out for n in NAMES):
         sys.exit(f"compare_volumes: {args.pred} and {args.truth} share neither static.npy nor dynamic.npy")
     text = json.dumps(out, indent=1)
