@@ -957,6 +957,51 @@ int nca_vol_overlap_sums(const NcaGrid* grid, const float* a, const float* b, in
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_skel_last_error(void);
 
+/* ---- label: the connected components of thresholded voxel stacks (metrics.label / component_sizes / keep_largest / component_report) --------
+ * What scipy.ndimage.label(vol > threshold, generate_binary_structure(3, connectivity)) returns, numbering included, for every volume of a
+ * stack; and the node count of every label.  Purely additive to ABI 13.  Like the other view sections these entry points keep their OWN
+ * per-thread message (the accessor below); a refused call launches nothing and reads no device pointer; a launch failure is reported once.
+ * vol is f32 [n_vol][n0][n1][n2] contiguous on the device, on one NcaGrid (`grid` is a host pointer; lo and inv are validated but unused:
+ * neighbourhoods count in nodes).  Every volume is labelled on its own: its result does not depend on n_vol or on its neighbours in the stack.
+ *
+ * LABEL.  For one volume:
+ *     node j is ON THE MASK iff ((double)vol[j] > threshold) != (invert != 0), the rule of nca_vol_edt: a NaN value and a value equal to
+ *         the threshold are on the mask only under invert;
+ *     two nodes of the mask are NEIGHBOURS iff their indices differ by at most 1 along every axis and along at least one and at most
+ *         `connectivity` axes: connectivity 1 / 2 / 3 gives 6 / 18 / 26 neighbours, scipy.ndimage.generate_binary_structure(3, connectivity);
+ *     a COMPONENT is a class of the transitive closure of that relation on the mask;
+ *     the components are numbered 1 .. count in increasing order of their smallest linear node index (i0 n1 + i1) n2 + i2: first
+ *         encounter in raster order, scipy.ndimage.label's numbering;
+ *     labels[j] (int32) = the number of j's component on the mask, 0 elsewhere;   counts[v] (int32) = count.
+ * The result is a function of the mask alone: the same bits on every run, although the kernels use atomics.
+ * Six launches: a union-find in LDS over every tile of 4 x 8 x 64 nodes; the unions across tile faces, edges and corners in global memory
+ * (a returning atomicMin links the larger root under the smaller); a read-only flattening that writes every node's root and counts the
+ * roots per 1024 nodes; the scan of those counts per volume; the numbering of the roots; the relabelling of every node from its root.  No
+ * launch waits for another workgroup and every loop is bounded by the node count (csrc/view/nca_label.hip states why).  No line is staged, so
+ * the tiling sets no limit on an axis.  labels may NOT alias vol (labels == vol is refused; an overlap is not detected).
+ * The workspace holds the root of every node as int32 and one int32 per 1024 nodes of every volume:
+ *     round256(4 n_vol n0 n1 n2) + round256(4 n_vol ceil(n0 n1 n2 / 1024)) bytes,   round256(b) = b rounded up to a multiple of 256.
+ * The query returns it, and 0 for arguments the entry point refuses.
+ * NCA_E_INVALID (the message names the value): a NULL grid, vol, labels or counts; labels == vol; n_vol <= 0; invert not 0 / 1; a threshold
+ * that is NaN; the grid refusals of nca_drr_project; more than 2^31 - 1 tiles of 4 x 8 x 64 nodes in the stack (what one launch covers).
+ * NCA_E_UNSUPPORTED: a connectivity other than 1, 2 or 3; a volume of more than 2^31 - 2 nodes (a label is a node index plus one in int32).
+ * NCA_E_WORKSPACE: work is NULL or work_bytes is below the query's answer. */
+size_t nca_vol_label_workspace(const NcaGrid* grid, int32_t n_vol);
+int nca_vol_label(const NcaGrid* grid, const float* vol, int32_t n_vol, double threshold, int32_t connectivity, int32_t invert, int32_t* labels,
+                  int32_t* counts, void* work, size_t work_bytes, void* stream);
+
+/* COMPONENT SIZES.  labels int32 [n_vol][n0][n1][n2] on the device (any labels, nca_vol_label's or not); sizes int32 [n_vol][cap] on the device:
+ *     sizes[v cap + l] = the number of nodes of volume v whose label is l, for 0 <= l < cap: entry 0 is the background.
+ * A label outside [0, cap) is not counted.  The entry point zeroes `sizes` itself (a memset on the stream), then one launch: runs of equal
+ * labels are merged within a wave, then per workgroup of 4096 nodes in a table of 256 slots in LDS, and every slot is one integer atomicAdd
+ * -- exact in any order, the same bits on every run.  No workspace.
+ * NCA_E_INVALID: a NULL grid, labels or sizes; n_vol <= 0; cap <= 0; the grid refusals of nca_drr_project; more than 2^24 workgroups.
+ * NCA_E_UNSUPPORTED: a volume of more than 2^31 - 2 nodes. */
+int nca_vol_label_sizes(const NcaGrid* grid, const int32_t* labels, int32_t n_vol, int32_t cap, int32_t* sizes, void* stream);
+
+/* The message of the calling thread's last failed call of this section. */
+const char* nca_label_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

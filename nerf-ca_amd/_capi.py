@@ -249,6 +249,10 @@ SYMBOLS = {
     "nca_vol_overlap_sums_workspace": (C.c_size_t, [C.POINTER(NcaGrid), _I32]),
     "nca_vol_overlap_sums": (C.c_int, [C.POINTER(NcaGrid), _P, _P, _I32, _P, _P, C.c_size_t, _P]),
     "nca_skel_last_error": (C.c_char_p, []),
+    "nca_vol_label_workspace": (C.c_size_t, [C.POINTER(NcaGrid), _I32]),
+    "nca_vol_label": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, _I32, _I32, _P, _P, _P, C.c_size_t, _P]),
+    "nca_vol_label_sizes": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, _I32, _P, _P]),
+    "nca_label_last_error": (C.c_char_p, []),
 }
 
 
@@ -296,6 +300,7 @@ check_edt = _section_check("nca_edt_last_error", "distance-transform entry point
 check_filt = _section_check("nca_filt_last_error", "filter entry points (nca_vol_smooth*, nca_vol_cityblock*)")
 check_resample = _section_check("nca_resample_last_error", "resampling entry points (nca_vol_spline_filter, nca_vol_zoom*)")
 check_skel = _section_check("nca_skel_last_error", "soft-skeleton entry points (nca_vol_softskel*, nca_vol_overlap_sums*)")
+check_label = _section_check("nca_label_last_error", "connected-component entry points (nca_vol_label*)")
 
 
 def ptr(t) -> Optional[int]:

@@ -17,6 +17,11 @@ implementation behind ``distance_transform``.
 (``nca_vol_softskel``; include/nerfca_hip.h, "skel"), and ``cldice`` the centreline Dice of two stacks: how much of each volume's
 skeleton lies inside the other volume.  It judges the topology of a vessel where the Dice coefficient only counts shared nodes, and it
 needs no analytic centreline.  There is no torch implementation behind ``soft_skeleton``.
+
+``label`` numbers the connected components of a thresholded stack as ``scipy.ndimage.label`` does (``nca_vol_label``; include/nerfca_hip.h,
+"label": a union-find over the voxel grid), ``component_sizes`` counts their nodes, ``keep_largest`` reduces a mask to its largest
+components and ``component_report`` sets the component counts of a prediction and the truth side by side: is the fit one tree, or a tree
+plus speckle?  There is no torch implementation behind ``label``.
 """
 from __future__ import annotations
 
@@ -486,3 +491,173 @@ def cldice(pred: torch.Tensor, truth: torch.Tensor, *, iterations: int, threshol
     b = _overlap_sums(soft_skeleton(t, K), p, who)
     out = _cldice_of_sums(a[:, 0], a[:, 1], b[:, 0], b[:, 1], smooth)
     return {k: v.reshape(lead) for k, v in out.items()}
+
+
+# ----------------------------------------------------------------------------- connected components
+def _connectivity(connectivity, who):
+    c = int(connectivity)
+    if c != connectivity or isinstance(connectivity, bool) or c not in (1, 2, 3):
+        raise _capi.NcaError(f"{who}: connectivity = {connectivity!r} is not 1, 2 or 3 (6, 18 or 26 neighbours)")
+    return c
+
+
+def _keep_rule(k, min_size, who):
+    """(k, min_size) with exactly one of them deciding: ``min_size`` when given (``k`` must then be left at 1), else ``k >= 1``."""
+    if min_size is not None:
+        m = int(min_size)
+        if k != 1:
+            raise _capi.NcaError(f"{who}: k = {k!r} and min_size = {min_size!r} are both given: one of them decides")
+        if m != min_size or isinstance(min_size, bool) or m < 1:
+            raise _capi.NcaError(f"{who}: min_size = {min_size!r} is not a whole number >= 1")
+        return None, m
+    n = int(k)
+    if n != k or isinstance(k, bool) or n < 1:
+        raise _capi.NcaError(f"{who}: k = {k!r} is not a whole number >= 1")
+    return n, None
+
+
+@torch.no_grad()
+def label(vol: torch.Tensor, *, threshold: float, connectivity: int = 1, invert: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The connected components of ``M = vol > threshold`` (``~(vol > threshold)`` with ``invert``) of every volume of the f32 stack
+    ``vol`` ``[..., n0, n1, n2]`` on the device: ``(labels, counts)`` with ``labels`` int32 of the same shape -- the component's number
+    ``1 .. count`` on the mask, 0 elsewhere -- and ``counts`` int64 of the leading shape.  A bool mask is accepted too, with a ``threshold``
+    in [0, 1).  A NaN value is not ``> threshold``.
+
+    Two nodes of the mask are neighbours when they differ by at most 1 along every axis and in at most ``connectivity`` axes: 1 / 2 / 3
+    gives 6 / 18 / 26 neighbours (``scipy.ndimage.generate_binary_structure(3, connectivity)``; the default is scipy's).  The components of
+    a volume are numbered in increasing order of their smallest linear node index.  This is
+    ``scipy.ndimage.label(vol > threshold, generate_binary_structure(3, connectivity))``, numbering included, for every volume on its own.
+
+    One ``nca_vol_label`` (six launches: a union-find in LDS per tile, the unions across tiles, flattening, the ranking of the roots, the
+    relabelling; the definition is in include/nerfca_hip.h, "label").  The result is a function of the mask alone: the same bits on every
+    run.  Nothing is read back.  Not differentiable.  A volume of more than 2^31 - 2 nodes is refused."""
+    who = "label"
+    x_in = _skel_input(vol, None, who)          # refused before the threshold is looked at
+    threshold = _view.finite_threshold(threshold, who)
+    conn = _connectivity(connectivity, who)
+    desc, x, n_vol, _ = _view.volume_stack(x_in, who)
+    labels = torch.empty(x.shape, dtype=torch.int32, device=x.device)
+    counts = torch.empty((n_vol,), dtype=torch.int32, device=x.device)
+    lib = _capi.lib()
+    nbytes = int(lib.nca_vol_label_workspace(C.byref(desc), n_vol))
+    work = _view.workspace(nbytes, x.device)
+    _view.launch(_capi.check_label, lib.nca_vol_label, x.device, C.byref(desc), _capi.ptr(x), n_vol, threshold, conn, 1 if invert else 0, _capi.ptr(labels),
+                 _capi.ptr(counts), _capi.ptr(work), nbytes)
+    return labels.reshape(vol.shape), counts.to(torch.int64).reshape(vol.shape[:-3])
+
+
+def _check_labels(labels, counts, who):
+    if not isinstance(labels, torch.Tensor) or not isinstance(counts, torch.Tensor):
+        raise _capi.NcaError(f"{who}: labels and counts are tensors, as label returns them")
+    if labels.dtype != torch.int32 or labels.dim() < 3 or labels.numel() == 0:
+        raise _capi.NcaError(f"{who} takes int32 labels [..., n0, n1, n2], got {labels.dtype} {tuple(labels.shape)}")
+    if counts.dtype != torch.int64 or counts.shape != labels.shape[:-3]:
+        raise _capi.NcaError(f"{who}: counts is int64 of the leading shape {tuple(labels.shape[:-3])}, got {counts.dtype} {tuple(counts.shape)}")
+    if counts.device != labels.device:
+        raise _capi.NcaError(f"{who}: labels live on {labels.device}, counts on {counts.device}")
+
+
+@torch.no_grad()
+def component_sizes(labels: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
+    """The node count of every component: int64 ``[..., max_count + 1]`` from the ``(labels, counts)`` of ``label``.  Entry 0 is the
+    background, entry ``l`` the component numbered ``l``; entries past a volume's own count are 0.  A stack with no component at all returns
+    the single background column.  Reading ``counts.max()`` is the one host sync; then one ``nca_vol_label_sizes`` (integer atomics, merged
+    per wave and per workgroup first: exact in any order)."""
+    who = "component_sizes"
+    _check_labels(labels, counts, who)
+    _fused._require_cuda(labels, "labels")
+    lead, shape = labels.shape[:-3], tuple(labels.shape[-3:])
+    x = labels.reshape((-1,) + shape).contiguous()
+    cap = int(counts.max()) + 1
+    if cap < 1:
+        raise _capi.NcaError(f"{who}: counts holds a negative count")
+    desc = _capi.grid_desc(shape, tuple((0.0, float(n - 1)) for n in shape))
+    sizes = torch.empty((x.shape[0], cap), dtype=torch.int32, device=x.device)
+    _view.launch(_capi.check_label, _capi.lib().nca_vol_label_sizes, x.device, C.byref(desc), _capi.ptr(x), x.shape[0], cap, _capi.ptr(sizes))
+    return sizes.to(torch.int64).reshape(lead + (cap,))
+
+
+@torch.no_grad()
+def largest_components(labels: torch.Tensor, sizes: torch.Tensor, k: int = 1, *, min_size: Optional[int] = None) -> torch.Tensor:
+    """The selection of ``keep_largest`` from ``labels`` ``[..., n0, n1, n2]`` (any integer dtype) and their ``sizes`` ``[..., cap]`` as
+    ``component_sizes`` returns them: the bool mask of the nodes whose component is among the ``k`` largest of its volume (ties go to the
+    smaller label; a volume with fewer components keeps all), or, with ``min_size``, has at least that many nodes.  Plain torch on whatever
+    device the tensors live on."""
+    who = "keep_largest"
+    k, min_size = _keep_rule(k, min_size, who)
+    if labels.dim() < 3 or sizes.dim() != labels.dim() - 2 or sizes.shape[:-1] != labels.shape[:-3]:
+        raise _capi.NcaError(f"{who}: labels {tuple(labels.shape)} and sizes {tuple(sizes.shape)} do not belong together")
+    cap = sizes.shape[-1]
+    s = sizes.reshape(-1, cap).to(torch.int64)
+    comp = s[:, 1:]
+    if min_size is not None:
+        keep_comp = comp >= min_size
+    else:
+        order = torch.sort(comp, dim=1, descending=True, stable=True)[1]          # stable: among equal sizes the smaller label comes first
+        keep_comp = torch.zeros_like(comp, dtype=torch.bool)
+        keep_comp.scatter_(1, order[:, :k], True)
+        keep_comp &= comp > 0          # a number no node carries
+    keep = torch.cat([torch.zeros((s.shape[0], 1), dtype=torch.bool, device=s.device), keep_comp], dim=1)
+    flat = labels.reshape(s.shape[0], -1).to(torch.int64)
+    return torch.gather(keep, 1, flat).reshape(labels.shape)
+
+
+@torch.no_grad()
+def keep_largest(vol: torch.Tensor, k: int = 1, *, threshold: float, connectivity: int = 3, min_size: Optional[int] = None) -> torch.Tensor:
+    """The mask ``vol > threshold`` of an f32 stack ``[..., n0, n1, n2]`` on the device (or a bool mask, ``threshold`` in [0, 1)) reduced to
+    the ``k`` largest components of every volume, as a bool tensor of the same shape: the usual cleanup of a thresholded vessel before a
+    surface distance.  Components are those of ``label`` at ``connectivity`` (26 neighbours by default: a vessel one node wide may run
+    diagonally).  Ties in size go to the smaller label -- the component that comes first in raster order -- so the result is the same on
+    every run.  A volume with fewer than ``k`` components keeps all of them.  With ``min_size`` every component of at least that many nodes
+    is kept instead, however many there are.  Exactly one of the two decides: ``min_size`` together with a ``k`` other than 1, or
+    ``k < 1``, is refused.
+
+    ``label``, ``component_sizes`` (one host sync for the largest count) and a sort of the sizes in torch."""
+    who = "keep_largest"
+    _keep_rule(k, min_size, who)          # refused before anything runs
+    labels, counts = label(_skel_input(vol, None, who), threshold=threshold, connectivity=connectivity)
+    return largest_components(labels, component_sizes(labels, counts), k, min_size=min_size)
+
+
+@torch.no_grad()
+def component_report_reductions(counts_pred: torch.Tensor, sizes_pred: torch.Tensor, counts_truth: torch.Tensor, sizes_truth: torch.Tensor) -> dict:
+    """The reductions of ``component_report`` from the ``counts`` ``[...]`` and ``sizes`` ``[..., cap]`` of the two stacks (the two caps may
+    differ): plain torch on whatever device the tensors live on."""
+    if counts_pred.shape != counts_truth.shape or sizes_pred.shape[:-1] != counts_pred.shape or sizes_truth.shape[:-1] != counts_truth.shape:
+        raise _capi.NcaError(f"component_report: counts {tuple(counts_pred.shape)}, {tuple(counts_truth.shape)} and sizes {tuple(sizes_pred.shape)}, "
+                             f"{tuple(sizes_truth.shape)} do not belong together")
+
+    def share(sizes):
+        comp = sizes[..., 1:].to(torch.int64)
+        total = comp.sum(dim=-1)
+        top = comp.amax(dim=-1) if comp.shape[-1] else torch.zeros_like(total)
+        nan = torch.full((), math.nan, dtype=torch.float64, device=sizes.device)
+        return torch.where(total == 0, nan, top.double() / total.double())
+
+    cp, ct = counts_pred.to(torch.int64), counts_truth.to(torch.int64)
+    return {"components_pred": cp, "components_truth": ct, "betti0_error": (cp - ct).abs(), "largest_share_pred": share(sizes_pred),
+            "largest_share_truth": share(sizes_truth)}
+
+
+@torch.no_grad()
+def component_report(pred: torch.Tensor, truth: torch.Tensor, *, threshold: float, pred_threshold: Optional[float] = None, connectivity: int = 3) -> dict:
+    """Is the prediction one tree, or a tree plus speckle?  For the masks ``pred > pred_threshold`` (``threshold`` when ``pred_threshold`` is
+    ``None``) and ``truth > threshold`` of two f32 stacks ``[..., n0, n1, n2]`` of one shape on the device (bool masks are accepted), per
+    volume, as device tensors of the leading shape:
+
+        ``components_pred``, ``components_truth``     the component counts of ``label`` at ``connectivity`` (i64),
+        ``betti0_error``                              their absolute difference, the Betti-0 error reported beside clDice (i64),
+        ``largest_share_pred``, ``largest_share_truth``   the nodes of the largest component over the nodes of the mask (f64; NaN for an
+                                                      empty mask): 1 for a single tree, lower the more of the mask is debris.
+
+    Two ``label`` and two ``component_sizes`` calls (one host sync each)."""
+    who = "component_report"
+    p, t = _skel_input(pred, None, who, "pred"), _skel_input(truth, None, who, "truth")
+    if p.shape != t.shape:
+        raise _capi.NcaError(f"{who} takes two stacks of one shape, got {tuple(p.shape)} and {tuple(t.shape)}")
+    if p.device != t.device:
+        raise _capi.NcaError(f"{who}: pred lives on {p.device}, truth on {t.device}")
+    pthr = threshold if pred_threshold is None else pred_threshold
+    lp, cp = label(p, threshold=pthr, connectivity=connectivity)
+    lt, ct = label(t, threshold=threshold, connectivity=connectivity)
+    return component_report_reductions(cp, component_sizes(lp, cp), ct, component_sizes(lt, ct))

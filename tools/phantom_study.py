@@ -25,7 +25,10 @@ mean symmetric distance `assd` and the 95th-percentile Hausdorff distance `hd95`
 (> a quarter of the fit's OWN maximum: the fits top out far below rho), in units of the node spacing, averaged over the phases, and the
 share of the true centreline (phantom.centreline_points at half a node spacing) within one cell diagonal of the fit's mask.  Without the
 option the output is what it was.  --cldice K (with --distances) adds a fourth: the centreline Dice of the same two masks at K skeleton
-iterations (metrics.cldice), averaged over the phases -- graded where the Dice coefficient of the masks is 0.
+iterations (metrics.cldice), averaged over the phases -- graded where the Dice coefficient of the masks is 0.  --components (with
+--distances) adds the component count of the fit's mask (metrics.component_report, 26 neighbours; the truth's count beside it), the share of
+its largest component, and `assd` and `hd95` once more for the fit's mask reduced to its --keep-largest K largest components (K = 1 by
+default; metrics.keep_largest), all averaged over the phases: how much of the distances is debris and how much is the artery.
 
 These numbers are recorded and gated nowhere.
 
@@ -60,7 +63,7 @@ def ssim_rows(ssim_weights):
     return [(tv_space, 0.0, w) for w in ssim_weights for tv_space in (0.0, 1e-5)]
 
 
-def distance_columns(fit_dynamic, dynamic, bounds, segments, threshold, cldice=None):
+def distance_columns(fit_dynamic, dynamic, bounds, segments, threshold, cldice=None, keep=None):
     """{"assd_cells", "hd95_cells", "centreline_coverage", ...}: the means over the phases, distances in units of the node spacing."""
     from nerfca_amd import metrics, phantom
     side = dynamic.shape[-1]
@@ -74,6 +77,14 @@ def distance_columns(fit_dynamic, dynamic, bounds, segments, threshold, cldice=N
     if cldice is not None:
         t = metrics.cldice(fit_dynamic, dynamic, iterations=cldice, threshold=threshold, pred_threshold=own)
         extra = {"cldice_iterations": cldice, "cldice": float(t["cldice"].mean()), "tprec": float(t["tprec"].mean()), "tsens": float(t["tsens"].mean())}
+    if keep is not None:
+        r = metrics.component_report(fit_dynamic, dynamic, threshold=threshold, pred_threshold=own)
+        kept = metrics.keep_largest(fit_dynamic, keep, threshold=own).to(torch.float32)
+        k = metrics.mask_distances(kept, (dynamic > threshold).to(torch.float32), bounds, threshold=0.5)
+        extra.update({"keep_largest": keep, "components": float(r["components_pred"].double().mean()), "components_truth": float(r["components_truth"].double().mean()),
+                      "betti0_error": float(r["betti0_error"].double().mean()), "largest_share": float(r["largest_share_pred"].mean()),
+                      "assd_cleaned_cells": float(k["assd"].mean()) / cell, "hd95_cleaned_cells": float(k["hd_percentile"].mean()) / cell,
+                      "hausdorff_cleaned_cells": float(k["hausdorff"].mean()) / cell, "n_cleaned_mean": float(k["n_pred"].double().mean())})
     return {**extra, "pred_threshold": own, "assd_cells": float(d["assd"].mean()) / cell, "hd95_cells": float(d["hd_percentile"].mean()) / cell,
             "hausdorff_cells": float(d["hausdorff"].mean()) / cell, "pred_to_truth_cells": float(d["pred_to_truth"].mean()) / cell,
             "truth_to_pred_cells": float(d["truth_to_pred"].mean()) / cell, "n_pred_mean": float(d["n_pred"].double().mean()),
@@ -81,7 +92,7 @@ def distance_columns(fit_dynamic, dynamic, bounds, segments, threshold, cldice=N
             "centreline_mean_distance_cells": float(c["mean_distance"].mean()) / cell}
 
 
-def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice=None):
+def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice=None, keep=None):
     from nerfca_amd import drr, metrics, phantom, synthetic
     geo = synthetic.xcat_geometry(n_det)
     ph = phantom.make_phantom((side,) * 3, PHASES, geo, device=dev)
@@ -111,7 +122,7 @@ def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice
                      "rmse_sum": e_sum["rmse"], "dice_vessels": e_d["dice"], "dice_vessels_low": e_low["dice"], "dynamic_max": float(fit["dynamic"].max()), "truth_dynamic_max": float(dynamic.max()), "psnr_held_out": psnr(again, held),
                      "ssim_weight": ssim_weight, "ssim_held_out": float(metrics.ssim(again, held, data_range=held_range).mean())})
         if distances:
-            rows[-1].update(distance_columns(fit["dynamic"], dynamic, bounds, ph["segments"], threshold, cldice))
+            rows[-1].update(distance_columns(fit["dynamic"], dynamic, bounds, ph["segments"], threshold, cldice, keep))
         if "ssim" in fit:
             rows[-1].update({"ssim_train_first": fit["ssim"][0], "ssim_train_last": fit["ssim"][-1]})
         print(json.dumps(rows[-1]), flush=True)
@@ -151,6 +162,8 @@ def parser():
     ap.add_argument("--ssim-weight", default="", help="comma separated weights of the structural term: adds rows (default: none)")
     ap.add_argument("--distances", action="store_true", help="add the mask distances and the centreline coverage of the fitted dynamic stack")
     ap.add_argument("--cldice", type=int, default=None, metavar="K", help="with --distances: add the clDice of the fitted dynamic stack at K skeleton iterations")
+    ap.add_argument("--components", action="store_true", help="with --distances: add the component count, the largest component's share and the distances of the cleaned mask")
+    ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="with --components: the cleaned mask keeps the K largest components (default 1)")
     return ap
 
 
@@ -158,6 +171,13 @@ def main(argv=None):
     args = parser().parse_args(argv)
     if args.cldice is not None and not args.distances:
         sys.exit("phantom_study: --cldice is a column of the --distances study")
+    if args.components and not args.distances:
+        sys.exit("phantom_study: --components adds columns to the --distances study")
+    if args.keep_largest is not None and not args.components:
+        sys.exit("phantom_study: --keep-largest sets the cleaned mask of the --components columns")
+    if args.keep_largest is not None and args.keep_largest < 1:
+        sys.exit(f"phantom_study: --keep-largest {args.keep_largest} is not a whole number >= 1")
+    keep = (args.keep_largest or 1) if args.components else None
     if not torch.cuda.is_available():
         sys.exit("phantom_study needs the GPU")
     dev = torch.device("cuda:0")
@@ -165,18 +185,21 @@ def main(argv=None):
     ssim_weights = [float(w) for w in args.ssim_weight.split(",") if w.strip()]
     fits = []
     for side in sides:
-        fits += study(dev, side, args.n_det, args.samples, args.steps, args.lr, WEIGHTS + ssim_rows(ssim_weights), args.distances, args.cldice)[0]
+        fits += study(dev, side, args.n_det, args.samples, args.steps, args.lr, WEIGHTS + ssim_rows(ssim_weights), args.distances, args.cldice, keep)[0]
         torch.cuda.empty_cache()
     rep = reprojection(dev, sides, args.n_det, args.samples)
     table = [f"fit_volumes on the phantom, P = {PHASES}, 4 training views of {args.n_det}^2 pixels x {args.samples} samples, {args.steps} Adam steps at lr {args.lr}, from zeros",
              "volume  tv_space  tv_time   loss first -> last        rmse static  rmse dynamic  rmse sum   Dice >rho/4  Dice >rho/20  dynamic max (truth)  PSNR held-out (-5,40)   seconds   ssim_weight  SSIM held-out"
              + ("   assd (cells)  hd95 (cells)  centreline within a cell diagonal" if args.distances else "")
-             + (f"   clDice (K = {args.cldice})" if args.cldice is not None else "")]
+             + (f"   clDice (K = {args.cldice})" if args.cldice is not None else "")
+             + (f"   components (truth)  largest share   assd, hd95 of the {keep} largest (cells)" if keep is not None else "")]
     for r in fits:
         table.append(f"{r['volume']:>4}^3  {r['tv_space']:<8g}  {r['tv_time']:<7g}   {r['loss_first']:.3e} -> {r['loss_last']:.3e}   {r['rmse_static']:>10.4f}   {r['rmse_dynamic']:>10.4f}   "
                      f"{r['rmse_sum']:>8.4f}   {r['dice_vessels']:>10.4f}   {r['dice_vessels_low']:>10.4f}   {r['dynamic_max']:>8.3f} ({r['truth_dynamic_max']:.3f})   {r['psnr_held_out']:>12.2f} dB          {r['fit_seconds']:>7.1f}   {r['ssim_weight']:<11g}  {r['ssim_held_out']:.4f}"
                      + (f"         {r['assd_cells']:>7.3f}      {r['hd95_cells']:>7.3f}       {r['centreline_coverage']:.4f}" if args.distances else "")
-                     + (f"                      {r['cldice']:.4f}" if args.cldice is not None else ""))
+                     + (f"                      {r['cldice']:.4f}" if args.cldice is not None else "")
+                     + (f"      {r['components']:>8.1f} ({r['components_truth']:.1f})      {r['largest_share']:.4f}         {r['assd_cleaned_cells']:>7.3f}  {r['hd95_cleaned_cells']:>7.3f}"
+                        if keep is not None else ""))
     table.append(f"reprojection distance: the frames of the phantom rasterised at n^3 against those of the phantom at {FINE}^3 (4 views x {PHASES} phases)")
     for r in rep:
         table.append(f"{r['volume']:>4}^3   " + "   ".join(f"{k}: max {r[k]['max_abs']:.4e} rmse {r[k]['rmse']:.4e} PSNR {r[k]['psnr']:.2f} dB" for k in ("pred", "pred_static", "pred_dynamic")))
