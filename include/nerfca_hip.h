@@ -1002,6 +1002,69 @@ int nca_vol_label_sizes(const NcaGrid* grid, const int32_t* labels, int32_t n_vo
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_label_last_error(void);
 
+/* ---- vess: the multi-scale Hessian vesselness of voxel stacks (ccta.hessian_eigenvalues / vesselness) ---------------------------------------
+ * The tubeness of Frangi et al., "Multiscale vessel enhancement filtering" (MICCAI 1998), from the eigenvalues of the scale-normalised
+ * Hessian of an ALREADY SMOOTHED volume: one call per scale, everything after the Gaussian (nca_vol_smooth) in one launch.  Purely additive
+ * to ABI 13.  Like the other view sections these entry points keep their OWN per-thread message (the accessor below); a refused call
+ * launches nothing and reads no device pointer; a launch failure is reported once.  s is f32 [n_vol][n0][n1][n2] contiguous on the device,
+ * the volume smoothed at sigma, on one NcaGrid (`grid` is a host pointer; lo and inv are validated but unused: everything counts in nodes,
+ * so the spacing is taken as isotropic); scale = sigma^2.  Every volume is treated on its own: its result does not depend on n_vol or on
+ * its neighbours in the stack.  Every operation below is ONE rounded f64 operation in the order written (no fused multiply-add), so a
+ * transcription into any IEEE arithmetic has the same bits up to exp.
+ *
+ * HESSIAN at node i = (i0, i1, i2), in f64 from the f32 values.  Every index is clamped to [0, n_a - 1] on its own axis (edge replication);
+ * e_a is the unit step along axis a:
+ *     D_aa = (s[i + e_a] - s[i]) - (s[i] - s[i - e_a]);
+ *     D_ab = 0.25 * ((s[i + e_a + e_b] - s[i + e_a - e_b]) - (s[i - e_a + e_b] - s[i - e_a - e_b]))       for a < b;
+ *     H = scale * D, the six entries H_00, H_01, H_02, H_11, H_12, H_22.
+ * If any of the six is not finite, all three eigenvalues are NaN and the vesselness is +0; the solver is not run.
+ *
+ * EIGENVALUES.  Cyclic Jacobi on the symmetric a = H: exactly 5 sweeps, each over the pairs (p, q) = (0,1), (0,2), (1,2), r the third index.
+ * A pair with a_pq == 0 is skipped.  Otherwise
+ *     theta = (a_qq - a_pp) / (2 * a_pq);     t = sgn / (|theta| + sqrt(theta * theta + 1)),  sgn = -1 if theta < 0, else +1;
+ *     c = 1 / sqrt(t * t + 1);     s = t * c;
+ *     a_pp = a_pp - t * a_pq;     a_qq = a_qq + t * a_pq   (both from the old a_pq);     a_pq = 0;
+ *     (a_rp, a_rq) = (c * a_rp - s * a_rq,  s * a_rp + c * a_rq)   (both from the old pair).
+ * After 5 sweeps the diagonal is within 2^-49 |H|_F of the eigenvalues (measured against LAPACK on 10^6 matrices: random, nearly
+ * degenerate, tube-like, scaled over 10^+-16, small integers).  (x_0, x_1, x_2) = (a_00, a_11, a_22) is then sorted by three
+ * compare-and-swaps on the positions (0,1), (1,2), (0,1): x_i and x_j, i < j, change places iff |x_j| < |x_i|, or |x_j| == |x_i| and
+ * x_j < x_i.  (l1, l2, l3) = the result: ascending in absolute value, the smaller value first on a tie.  A NaN (an overflow inside the
+ * solver) swaps with nothing and is written as the canonical quiet NaN.
+ *
+ * VESSELNESS of bright tubes (bright = 1).  V = +0 unless l2 < 0 and l3 < 0; then, with c = c[v] of the node's volume,
+ *     Ra2 = (l2 * l2) / (l3 * l3);     Rb2 = (l1 * l1) / |l2 * l3|;     S2 = (l1 * l1 + l2 * l2) + l3 * l3;
+ *     A = 1 - exp(-Ra2 / (2 * (alpha * alpha)));     B = exp(-Rb2 / (2 * (beta * beta)));     C = 1 - exp(-S2 / (2 * (c * c))),  C = 1 if c == 0;
+ *     V = (A * B) * C, rounded once to f32.
+ * bright = 0 (dark tubes) takes l2 > 0 and l3 > 0 instead.  Every step above is odd or even in s bit for bit, so that is the bright
+ * vesselness of -s -- except at a node where two eigenvalues of opposite sign tie in absolute value, which the tie rule orders the same way
+ * for s and -s.  V lies in [0, 1].  c[v] is read on the device and not checked.
+ *
+ * nca_vol_hessian_eig: eig f32 [n_vol][3][n0][n1][n2] = (l1, l2, l3), each rounded once to f32.
+ * nca_vol_hessian_norm_max: norm_max f64 [n_vol] on the device, norm_max[v] = max(+0, the maximum over the nodes of volume v of
+ *     S2' = (x1 * x1 + x2 * x2) + x3 * x3,  x_j = l_j rounded to f32 and taken back to f64) -- the S2 of what nca_vol_hessian_eig writes, so
+ *     a caller can form the same number from eig.  max(a, b) = (b > a) ? b : a: a NaN is passed over, +inf is kept.  The entry point zeroes
+ *     norm_max itself (a memset on the stream); a workgroup takes the maximum of its tile in a tree and makes one integer atomicMax on the
+ *     bit pattern, which orders non-negative doubles as their values do: exact in any order, the same bits on every run.  Frangi's rule is
+ *     c = 0.5 sqrt(norm_max).
+ * nca_vol_vesselness: out f32 [n_vol][n0][n1][n2], scale_out int32 of the same shape or NULL.  scale_index == 0: every node of out is
+ *     written with V and every node of scale_out with 0.  scale_index > 0: out and scale_out are read-modify-write, a node is replaced by
+ *     (V, scale_index) only where V > out (the f32 values): over increasing scale_index the result is the maximum over the scales and the
+ *     SMALLEST index that attains it.
+ * One launch each (norm_max: a memset before it).  A workgroup owns a tile of 4 x 8 x 64 nodes, stages it with a halo of one node in LDS
+ * (6 x 10 x 66 f32), and each thread forms the 19-point stencil of its four nodes and runs the solver in registers.  Every node is written
+ * once by the thread that owns it.  No workspace.  The tiling sets no limit on an axis.  No output may be s itself (refused; an overlap is
+ * not detected).
+ * NCA_E_INVALID (the message names the value): a NULL grid, s, eig / norm_max / out or c; an output that is s; n_vol <= 0; the grid
+ * refusals of nca_drr_project; a scale, alpha or beta that is not finite and positive; bright not 0 / 1; scale_index < 0; more than
+ * 2^31 - 1 tiles of 4 x 8 x 64 nodes in the stack (what one launch covers). */
+int nca_vol_hessian_eig(const NcaGrid* grid, const float* s, int32_t n_vol, double scale, float* eig, void* stream);
+int nca_vol_hessian_norm_max(const NcaGrid* grid, const float* s, int32_t n_vol, double scale, double* norm_max, void* stream);
+int nca_vol_vesselness(const NcaGrid* grid, const float* s, int32_t n_vol, double scale, double alpha, double beta, const double* c, int32_t bright,
+                       int32_t scale_index, float* out, int32_t* scale_out, void* stream);
+
+/* The message of the calling thread's last failed call of this section. */
+const char* nca_vess_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,15 @@ volume on ``bounds`` to a target spacing with it, and ``prepare_ccta(resample=..
 "resample").  One deliberate difference from scipy: the last output node of an axis is always the last input node, where scipy writes 0
 into the whole last plane for the size pairs at which its coordinate overshoots by one ulp (4 -> 188 nodes, about 4 % of all pairs).
 
-Not here: spline orders 1, 2, 4 and 5, ``grid_mode``, file readers, other boundary modes, other structuring elements, gradients.
+``vesselness`` is the multi-scale Hessian tubeness of Frangi et al. (MICCAI 1998): per scale one ``gaussian_filter`` and one launch that
+forms the scale-normalised Hessian, its eigenvalues (five sweeps of cyclic Jacobi in f64) and the tubeness of every node, merged over the
+scales on the device; ``hessian_eigenvalues`` returns the sorted eigenvalues of one scale (csrc/view/nca_vess.hip; the definition,
+operation by operation, is in include/nerfca_hip.h, "vess").  It asks what shape a node's neighbourhood has -- bright, thin along two axes,
+long along the third -- where a threshold asks how dense the node is.
+
+Not here: spline orders 1, 2, 4 and 5, ``grid_mode``, file readers, other boundary modes, other structuring elements; for the vesselness,
+anisotropic spacing (everything counts in nodes: bring the volume to an isotropic grid with ``resample`` first), dark and bright tubes in
+one call, the 2-D filter; gradients of any of it.
 """
 from __future__ import annotations
 
@@ -356,3 +364,82 @@ def prepare_ccta(raw_hu: torch.Tensor, vessel_mask: torch.Tensor, bounds, *, lab
     dynamic, closed = vessel_contrast(m, depth_bounds, **vessel_kw)
     static = torch.where(closed, torch.zeros((), dtype=torch.float32, device=att.device), att.to(torch.float32))
     return {"static": static, "dynamic": dynamic, "mask": closed, "bounds": tuple((float(b[0]), float(b[1])) for b in bounds)}
+
+
+def _vess_sigmas(sigmas, who):
+    """The scales as floats: at least one, each finite and positive."""
+    try:
+        sig = [float(s) for s in sigmas]
+    except TypeError:
+        raise _capi.NcaError(f"{who}: sigmas = {sigmas!r} is not a sequence of numbers") from None
+    if not sig:
+        raise _capi.NcaError(f"{who}: sigmas is empty")
+    for s in sig:
+        if not (math.isfinite(s) and s > 0.0):
+            raise _capi.NcaError(f"{who}: sigma = {s} is not finite and positive")
+    return sig
+
+
+def _vess_param(value, name, who, zero_ok=False):
+    """alpha, beta (finite and positive) or c (finite and non-negative) as a float."""
+    v = float(value)
+    if not (math.isfinite(v) and (v > 0.0 or (zero_ok and v == 0.0))):
+        raise _capi.NcaError(f"{who}: {name} = {v} is not finite and {'non-negative' if zero_ok else 'positive'}")
+    return v
+
+
+@torch.no_grad()
+def hessian_eigenvalues(vol: torch.Tensor, sigma: float) -> torch.Tensor:
+    """The eigenvalues of the scale-normalised Hessian ``sigma^2 d^2/dx_a dx_b gaussian_filter(vol, sigma)`` at every node of the f32 stack
+    ``vol`` ``[..., n0, n1, n2]`` on the device, sorted by absolute value (the smaller value first on a tie): an f32 tensor
+    ``[..., 3, n0, n1, n2]``.  Second differences in nodes with the edge values repeated, five sweeps of cyclic Jacobi in f64 (within
+    ``2^-49`` of the matrix norm of LAPACK's), one rounding to f32; a node whose Hessian is not finite gets three NaN.
+
+    One ``gaussian_filter`` and one ``nca_vol_hessian_eig``: the same bits on every run.  Not differentiable."""
+    who = "hessian_eigenvalues"
+    _view.check_volume(vol, who)
+    sigma, = _vess_sigmas((sigma,), who)
+    desc, x, n_vol, shape = _view.volume_stack(gaussian_filter(vol, sigma), who)
+    out = torch.empty((n_vol, 3) + shape, dtype=torch.float32, device=x.device)
+    _view.launch(_capi.check_vess, _capi.lib().nca_vol_hessian_eig, x.device, C.byref(desc), _capi.ptr(x), n_vol, sigma * sigma, _capi.ptr(out))
+    return out.reshape(tuple(vol.shape[:-3]) + (3,) + shape)
+
+
+@torch.no_grad()
+def vesselness(vol: torch.Tensor, sigmas: Sequence[float] = (1.0, 2.0, 3.0), *, alpha: float = 0.5, beta: float = 0.5, c: Optional[float] = None,
+               bright: bool = True, return_scale: bool = False):
+    """The multi-scale Hessian vesselness of Frangi et al. (MICCAI 1998) of every volume of the f32 stack ``vol`` ``[..., n0, n1, n2]`` on
+    the device: an f32 tensor of the same shape with values in [0, 1], the largest response over ``sigmas`` (in nodes).  With
+    ``return_scale`` also an int32 tensor of the same shape: the index into ``sigmas`` of the scale that gave it, the smallest on a tie.
+
+    With the eigenvalues ``|l1| <= |l2| <= |l3|`` of ``hessian_eigenvalues(vol, sigma)`` a node responds only where ``l2 < 0`` and
+    ``l3 < 0`` (``bright=False``: both ``> 0``, tubes darker than their surroundings):
+    ``V = (1 - exp(-(l2 / l3)^2 / (2 alpha^2))) exp(-l1^2 / |l2 l3| / (2 beta^2)) (1 - exp(-(l1^2 + l2^2 + l3^2) / (2 c^2)))``.
+    ``c=None`` is Frangi's rule, half the largest Hessian norm ``sqrt(l1^2 + l2^2 + l3^2)`` of each volume at each scale, formed on the
+    device; ``c=0`` drops the last factor.  A node whose Hessian is not finite gets 0.
+
+    Per scale one ``gaussian_filter(vol, sigma)`` (truncate 4: a sigma above 8.1 exceeds its radius limit of 32), one
+    ``nca_vol_hessian_norm_max`` when ``c`` is None, and one ``nca_vol_vesselness``; nothing is read back to the host and the bits are the
+    same on every run.  The spacing is taken as isotropic.  Not differentiable: it runs under ``no_grad`` and the result is detached."""
+    who = "vesselness"
+    _view.check_volume(vol, who)
+    sig = _vess_sigmas(sigmas, who)
+    alpha, beta = _vess_param(alpha, "alpha", who), _vess_param(beta, "beta", who)
+    if c is not None:
+        c = _vess_param(c, "c", who, zero_ok=True)
+    desc, x, n_vol, shape = _view.volume_stack(vol, who)
+    out = torch.empty_like(x)
+    index = torch.empty(x.shape, dtype=torch.int32, device=x.device) if return_scale else None
+    lib = _capi.lib()
+    for i, sigma in enumerate(sig):
+        s, scale = gaussian_filter(x, sigma), sigma * sigma
+        if c is None:
+            c_vol = torch.empty(n_vol, dtype=torch.float64, device=x.device)
+            _view.launch(_capi.check_vess, lib.nca_vol_hessian_norm_max, x.device, C.byref(desc), _capi.ptr(s), n_vol, scale, _capi.ptr(c_vol))
+            c_vol = 0.5 * torch.sqrt(c_vol)
+        else:
+            c_vol = torch.full((n_vol,), c, dtype=torch.float64, device=x.device)
+        _view.launch(_capi.check_vess, lib.nca_vol_vesselness, x.device, C.byref(desc), _capi.ptr(s), n_vol, scale, alpha, beta, _capi.ptr(c_vol),
+                     1 if bright else 0, i, _capi.ptr(out), _capi.ptr(index))
+    out = out.reshape(vol.shape)
+    return (out, index.reshape(vol.shape)) if return_scale else out

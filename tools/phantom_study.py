@@ -29,6 +29,10 @@ iterations (metrics.cldice), averaged over the phases -- graded where the Dice c
 --distances) adds the component count of the fit's mask (metrics.component_report, 26 neighbours; the truth's count beside it), the share of
 its largest component, and `assd` and `hd95` once more for the fit's mask reduced to its --keep-largest K largest components (K = 1 by
 default; metrics.keep_largest), all averaged over the phases: how much of the distances is debris and how much is the artery.
+--vesselness (with --distances, --cldice and --components) adds, after every fit, a row in which the fitted dynamic stack is replaced by
+its multi-scale Hessian vesselness (ccta.vesselness at --vesselness-sigmas, Frangi's c) before it is thresholded at a quarter of its own
+maximum, with the same columns against the same truth, and a second table that sets the two inputs side by side, with the Dice
+coefficient of the two masks.
 
 These numbers are recorded and gated nowhere.
 
@@ -92,8 +96,16 @@ def distance_columns(fit_dynamic, dynamic, bounds, segments, threshold, cldice=N
             "centreline_mean_distance_cells": float(c["mean_distance"].mean()) / cell}
 
 
-def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice=None, keep=None):
-    from nerfca_amd import drr, metrics, phantom, synthetic
+def mask_dice(pred, truth, pred_threshold, threshold):
+    """The Dice coefficient of pred > pred_threshold and truth > threshold per volume, averaged over the phases."""
+    a, b = pred > pred_threshold, truth > threshold
+    dims = (-3, -2, -1)
+    return float((2.0 * (a & b).sum(dims).double() / (a.sum(dims).double() + b.sum(dims).double())).mean())
+
+
+def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice=None, keep=None, vesselness=None):
+    """The rows of one grid size; with `vesselness` (the sigmas) also the side-by-side rows of the fit and of its vesselness."""
+    from nerfca_amd import ccta, drr, metrics, phantom, synthetic
     geo = synthetic.xcat_geometry(n_det)
     ph = phantom.make_phantom((side,) * 3, PHASES, geo, device=dev)
     bounds, static, dynamic = ph["bounds"], ph["static"], ph["dynamic"]
@@ -102,7 +114,7 @@ def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice
     held = drr.project_sequence(static, dynamic, geo, [HELD_OUT], samples, bounds=bounds)["pred"]
     frames = [(theta, phi, p, train[v, p].contiguous()) for v, (theta, phi) in enumerate(views) for p in range(PHASES)]
     threshold = 0.25 * phantom.RHO_VESSEL
-    rows = []
+    rows, pairs = [], []
     held_range = held.amax(dim=(-2, -1)).double() - held.amin(dim=(-2, -1)).double()
     for tv_space, tv_time, *rest in weights:
         ssim_weight = rest[0] if rest else 0.0
@@ -126,7 +138,14 @@ def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice
         if "ssim" in fit:
             rows[-1].update({"ssim_train_first": fit["ssim"][0], "ssim_train_last": fit["ssim"][-1]})
         print(json.dumps(rows[-1]), flush=True)
-    return rows, (geo, views, samples, train)
+        if vesselness:
+            V = ccta.vesselness(fit["dynamic"], vesselness)
+            for name, x in (("density", fit["dynamic"]), ("vesselness", V)):
+                cols = distance_columns(x, dynamic, bounds, ph["segments"], threshold, cldice, keep)
+                pairs.append({"volume": side, "tv_space": tv_space, "tv_time": tv_time, "ssim_weight": ssim_weight, "input": name, "sigmas": list(vesselness),
+                              "input_max": float(x.max()), "dice_own_quarter": mask_dice(x, dynamic, cols["pred_threshold"], threshold), **cols})
+                print(json.dumps(pairs[-1]), flush=True)
+    return rows, pairs
 
 
 def reprojection(dev, sides, n_det, samples):
@@ -164,6 +183,8 @@ def parser():
     ap.add_argument("--cldice", type=int, default=None, metavar="K", help="with --distances: add the clDice of the fitted dynamic stack at K skeleton iterations")
     ap.add_argument("--components", action="store_true", help="with --distances: add the component count, the largest component's share and the distances of the cleaned mask")
     ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="with --components: the cleaned mask keeps the K largest components (default 1)")
+    ap.add_argument("--vesselness", action="store_true", help="with --distances --cldice K --components: add rows for the vesselness of the fitted dynamic stack")
+    ap.add_argument("--vesselness-sigmas", default="1,2,3", help="its scales in nodes, comma separated")
     return ap
 
 
@@ -177,15 +198,20 @@ def main(argv=None):
         sys.exit("phantom_study: --keep-largest sets the cleaned mask of the --components columns")
     if args.keep_largest is not None and args.keep_largest < 1:
         sys.exit(f"phantom_study: --keep-largest {args.keep_largest} is not a whole number >= 1")
+    if args.vesselness and not (args.distances and args.cldice is not None and args.components):
+        sys.exit("phantom_study: --vesselness adds rows to the --distances --cldice K --components study")
+    vess_sigmas = tuple(float(s) for s in args.vesselness_sigmas.split(",")) if args.vesselness else None
     keep = (args.keep_largest or 1) if args.components else None
     if not torch.cuda.is_available():
         sys.exit("phantom_study needs the GPU")
     dev = torch.device("cuda:0")
     sides = tuple(int(s) for s in args.sides.split(","))
     ssim_weights = [float(w) for w in args.ssim_weight.split(",") if w.strip()]
-    fits = []
+    fits, pairs = [], []
     for side in sides:
-        fits += study(dev, side, args.n_det, args.samples, args.steps, args.lr, WEIGHTS + ssim_rows(ssim_weights), args.distances, args.cldice, keep)[0]
+        rows, both = study(dev, side, args.n_det, args.samples, args.steps, args.lr, WEIGHTS + ssim_rows(ssim_weights), args.distances, args.cldice, keep, vess_sigmas)
+        fits += rows
+        pairs += both
         torch.cuda.empty_cache()
     rep = reprojection(dev, sides, args.n_det, args.samples)
     table = [f"fit_volumes on the phantom, P = {PHASES}, 4 training views of {args.n_det}^2 pixels x {args.samples} samples, {args.steps} Adam steps at lr {args.lr}, from zeros",
@@ -200,13 +226,19 @@ def main(argv=None):
                      + (f"                      {r['cldice']:.4f}" if args.cldice is not None else "")
                      + (f"      {r['components']:>8.1f} ({r['components_truth']:.1f})      {r['largest_share']:.4f}         {r['assd_cleaned_cells']:>7.3f}  {r['hd95_cleaned_cells']:>7.3f}"
                         if keep is not None else ""))
+    if pairs:
+        table.append(f"the fitted dynamic stack and its vesselness (sigmas {args.vesselness_sigmas}, Frangi's c), each thresholded at a quarter of its own maximum, against the truth > rho / 4")
+        table.append(f"volume  tv_space  tv_time  input        max        Dice     assd (cells)  hd95 (cells)  clDice (K = {args.cldice})  components (truth)  largest share  centreline within a cell diagonal")
+        for r in pairs:
+            table.append(f"{r['volume']:>4}^3  {r['tv_space']:<8g}  {r['tv_time']:<7g}  {r['input']:<10}  {r['input_max']:>8.4f}   {r['dice_own_quarter']:.4f}      {r['assd_cells']:>7.3f}       {r['hd95_cells']:>7.3f}       "
+                         f"{r['cldice']:.4f}         {r['components']:>8.1f} ({r['components_truth']:.1f})       {r['largest_share']:.4f}        {r['centreline_coverage']:.4f}")
     table.append(f"reprojection distance: the frames of the phantom rasterised at n^3 against those of the phantom at {FINE}^3 (4 views x {PHASES} phases)")
     for r in rep:
         table.append(f"{r['volume']:>4}^3   " + "   ".join(f"{k}: max {r[k]['max_abs']:.4e} rmse {r[k]['rmse']:.4e} PSNR {r[k]['psnr']:.2f} dB" for k in ("pred", "pred_static", "pred_dynamic")))
     print("\n".join(table))
     if args.out:
         with open(args.out, "w") as f:
-            for r in fits + rep:
+            for r in fits + pairs + rep:
                 f.write(json.dumps(r) + "\n")
             f.write("\n".join(table) + "\n")
 
