@@ -4,7 +4,8 @@ the scalar every render-parity test differentiates,
     sum(pix * cp) + 50 sum(sigma_s * cs) + 50 sum(sigma_d * cd),
 
 launch counting, the bf16 bounds, the per-entry gradient checks on one-hot upstream gradients (nets with decided ReLU masks, the rank-one
-split, `scaled_err`, the ray and point cases with their memoised oracle gradients), what the launch-free tests of the view sections (csrc/view/) share: the `capi` / `lib` fixtures, the
+split, `scaled_err`, the ray and point cases with their memoised oracle gradients, the general kernels' cases with the restated launch arithmetic
+they are chosen by), what the launch-free tests of the view sections (csrc/view/) share: the `capi` / `lib` fixtures, the
 declared-bound-exported check, `refused` and the one list of NcaGrid refusals, and what their GPU tests share: `grid_of`, `same_bits`, `ulp_distance` and the raw launch of a
 workspace-taking entry point, `gpu_stack_call`.  Test modules import from here (and from conftest.py), never from one another.  Every helper
 draws from the generator it is given in a fixed, documented order: the tolerances of the tests were measured on those draws.
@@ -280,7 +281,18 @@ ONEHOT_NETS = {"F32_e1": (32, 1, 0), "F64_e2": (64, 2, 0), "F128_e3": (128, 3, 0
 # with 6 samples; 130: three tiles, the last with 2; 30 000: a window of its own for the dynamic net (the input block is not shared)
 ONEHOT_RAY_CASES = [(n, 70, 75000) for n in ONEHOT_NETS] + [("F64_e2", 130, 75000), ("F128_e3", 70, 30000)]
 ONEHOT_POINT_CASES = [("F32_e1", 130), ("F128_e3", 130), ("F128_e1_l2", 130), ("F144_e1", 300)]          # F = 144: the general kernels
-ONEHOT_POINT_NETS = dict(ONEHOT_NETS, F144_e1=(144, 1, 0))
+ONEHOT_POINT_NETS = dict(ONEHOT_NETS, F144_e1=(144, 1, 0), F144_e1_l2=(144, 1, 2), F64_e1=(64, 1, 0))
+# The general kernels at their tile, split and run seams (tests/test_onehot_general_cpu.py derives every launch shape named here again from
+# `general_launch_shapes` and asserts it; tests/test_onehot_general_gpu.py runs them).  Points: name -> (net, N, one-hot positions).
+GENERAL_POINT_CASES = {
+    "P1024": ("F144_e1", 1024, (0, 255, 320, 447, 512, 703, 831, 1023)),          # 8 row tiles: the remapped tile order, one position per tile
+    "P1100": ("F144_e1", 1100, (0, 1023, 1024, 1099)),                            # 9 row tiles: identity order, a last tile of 76 valid rows
+    "P16500": ("F144_e1", 16500, (143, 144, 8255, 16415, 16416, 16499)),          # 129 tiles, 128 splits of 144 rows, 13 of them empty
+    "PSKIP": ("F144_e1_l2", 300, (0, 127, 128, 299)),                             # the skip layer's two-segment contraction
+}
+GENERAL_CHANNEL_CASE = dict(cin=2, cout=3, F=48, early=2, late=1, pos_enc="vanilla", L=5, N=200, launches=((0, 0), (127, 2), (128, 1), (199, 2)))          # PCH: (n*, o*)
+# Rays: name -> (static net, S, width of the dynamic net when it differs).  RG: both nets on the general kernels; RMIX: one of them on the fused f32 kernels
+GENERAL_RAY_CASES = {"RG": ("F144_e1", 70, None), "RMIX_64_144": ("F64_e1", 70, 144), "RMIX_144_64": ("F144_e1", 70, 64)}
 BF_FACTOR = 2.0 ** -6          # check C, bf16 operands: one bf16 step is at most 2^-7 of a value, once on each factor
 
 
@@ -347,13 +359,14 @@ class OnehotRays(_OnehotOracle):
     """A static / dynamic pair of decided nets on one seeded batch of ONEHOT_R rays x S samples."""
     nets = "st"
 
-    def __init__(self, name, S, it_d):
+    def __init__(self, name, S, it_d, Fd=None):
         super().__init__()
-        F, early, late = ONEHOT_NETS[name]
+        F, early, late = ONEHOT_POINT_NETS[name]
         self.name, self.S, self.it_d, self.F, self.early, self.late = name, S, it_d, F, early, late
+        self.Fd = Fd or F                     # the dynamic net's width (Fd: where it differs from the static net's)
         self.early_d = max(early, 1)          # the dynamic net is plain (a Temporal with late layers has no output in the reference)
-        gen = torch.Generator().manual_seed(9100 + 7 * F + 3 * early + late + S + it_d // 1000)
-        self.ss, self.sd = spec_from(F, early, late), spec_from(F, self.early_d, 0, T=8)
+        gen = torch.Generator().manual_seed(9100 + 7 * F + 3 * early + late + S + it_d // 1000 + (11 * Fd if Fd else 0))
+        self.ss, self.sd = spec_from(F, early, late), spec_from(self.Fd, self.early_d, 0, T=8)
         self.win, self.win_d = O.freq_mask_alpha(12, 75000, 150000, 1)[0], O.freq_mask_alpha(12, it_d, 150000, 1)[0]
         self.o, self.d, self.ph, self.z, self.I0 = ray_inputs(ONEHOT_R, S, gen)[:5]
         self.dists = O.ray_dists(self.z, torch.float64)
@@ -386,7 +399,7 @@ class OnehotPoints(_OnehotOracle):
     """Decided nets on N seeded points for CPPN.forward / Temporal.forward_composite; launch i puts the one-hot `gout` at ns[i] (static
     net) and ns[i - 1] (dynamic net: a plain one beside a static net with a skip layer)."""
 
-    def __init__(self, name, N):
+    def __init__(self, name, N, ns=None):
         super().__init__()
         F, early, late = ONEHOT_POINT_NETS[name]
         self.name, self.N, self.F, self.early, self.late, self.early_d = name, N, F, early, late, max(early, 1)
@@ -398,8 +411,8 @@ class OnehotPoints(_OnehotOracle):
         self.ps, self.margin_s, self.feats_s = decided_params(self.ss, gen, O.encode(self.x, self.ss, self.win))
         self.pd, self.margin_d, self.feats_d = decided_params(self.sd, gen, O.encode(self.x, self.sd, self.win), phases=self.ts)
         self.nets = "st"
-        self.ns = [0, 63, 64, 129] if N == 130 else [0, 127, 128, N - 1]
-        self.launches = [(self.ns[i], self.ns[i - 1]) for i in range(4)]
+        self.ns = list(ns) if ns is not None else ([0, 63, 64, 129] if N == 130 else [0, 127, 128, N - 1])
+        self.launches = [(self.ns[i], self.ns[i - 1]) for i in range(len(self.ns))]
 
     def feats(self, net, n):
         return (self.feats_s if net == "s" else self.feats_d)[n]
@@ -424,6 +437,106 @@ def onehot_rays(name, S=70, it_d=75000):
 @functools.lru_cache(maxsize=None)
 def onehot_points(name, N):
     return OnehotPoints(name, N)
+
+
+class OnehotChannels(_OnehotOracle):
+    """PCH: one decided static net with other channel counts than 3 -> 1 (GENERAL_CHANNEL_CASE: the shape of test_wide_nets.CHANNEL_CASES[0]) on N seeded
+    points; launch i puts the one-hot `gout` at [n*, o*] = launches[i] -- one point AND one output channel."""
+    nets = "s"
+
+    def __init__(self):
+        super().__init__()
+        k = GENERAL_CHANNEL_CASE
+        self.name, self.N, self.F, self.early, self.late, self.cin, self.cout = "c2to3", k["N"], k["F"], k["early"], k["late"], k["cin"], k["cout"]
+        gen = torch.Generator().manual_seed(9900 + 7 * self.F + self.N)
+        self.ss = spec_from(self.F, self.early, self.late, k["pos_enc"], k["L"], cin=self.cin, cout=self.cout)
+        self.x = torch.rand(self.N, self.cin, generator=gen) * 2 - 1
+        self.ps, self.margin_s, self.feats_s = decided_params(self.ss, gen, O.encode(self.x, self.ss, None))
+        self.launches = list(k["launches"])
+
+    def feats(self, net, n):
+        return self.feats_s[n]
+
+    def _run(self, i, emu, dt):
+        n, o = self.launches[i]
+        p = {k: v.clone().to(dt).requires_grad_(True) for k, v in self.ps.items()}
+        O.static_forward(p, self.ss, self.x[n:n + 1].to(dt), None)[0, o].backward()
+        return {"s." + k: v.grad.detach() for k, v in p.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def general_case(name):
+    """The case `name` of GENERAL_POINT_CASES / GENERAL_RAY_CASES, or "PCH"."""
+    if name == "PCH":
+        return OnehotChannels()
+    if name in GENERAL_POINT_CASES:
+        net, N, ns = GENERAL_POINT_CASES[name]
+        return OnehotPoints(net, N, ns)
+    net, S, Fd = GENERAL_RAY_CASES[name]
+    return OnehotRays(net, S, 75000, Fd)
+
+
+def _up(a, b):
+    return (a + b - 1) // b * b
+
+
+def general_layout(F, NL, Kenc, T=0, P=0, cout=1, skip=None):
+    """What nca_build_layout_wide (nca_wide.hpp) derives of a net on the general kernels: K0 = Kenc + T, K0p = round_up(K0 + P, 16), the fan-in
+    Kp of every layer (layer 0: K0p; the skip layer `skip`: K0p + F; else F) and the floats of the packed image, which is also one split slab:
+    sum F Kp | biases NL F | Wo cout F | bo cout, rounded up to 4."""
+    K0 = Kenc + T
+    K0p = _up(K0 + P, 16)
+    Kp = [K0p if j == 0 else (K0p + F if j == skip else F) for j in range(NL)]
+    return dict(F=F, NL=NL, K0=K0, K0p=K0p, Kp=Kp, P=P, packed=_up(sum(F * k for k in Kp) + NL * F + cout * F + cout, 4))
+
+
+def general_plan(y, N, bwd=True, max_bytes=0):
+    """wide_plan of nca_api_wide.inc restated: (rows per chunk, nsplit, workspace bytes) of N samples under a workspace of max_bytes (0: no cap).
+        rows_all = align_up(N, 128); chunk = min(rows_all, 2^18); tiles = ceil(F / 128)^2; want = max(512 / tiles, 1)
+        nsplit = min(want, chunk / 128)
+        floats = chunk K0p + chunk F (bwd ? NL : 2) + (bwd ? (NL - 1) (chunk / 128) ceil(F / 128) 512 + 2 chunk F + nsplit packed + F P : 0)
+        over max_bytes and chunk > 128: chunk = align_up(chunk / 2, 128), again"""
+    F, NL = y["F"], y["NL"]
+    chunk = min(_up(N, 128), 1 << 18)
+    nt = (F + 127) // 128
+    want = max(512 // (nt * nt), 1)
+    while True:
+        nsplit = min(want, chunk // 128)
+        floats = chunk * y["K0p"] + chunk * F * (NL if bwd else 2)
+        if bwd:
+            floats += (NL - 1) * (chunk // 128) * nt * 512 + 2 * chunk * F + nsplit * y["packed"] + F * y["P"]
+        nbytes = _up(floats * 4, 256)
+        if max_bytes <= 0 or nbytes <= max_bytes or chunk <= 128:
+            return chunk, nsplit, nbytes
+        chunk = _up(chunk // 2, 128)
+
+
+def general_gemm_shape(kind, rows, cols, nsplit=1, ktot=0):
+    """The launch arithmetic of nca_wide_gemm (nca_kernels_wide.hip) restated:
+        nrt = ceil(rows / 128), nct = ceil(cols / 128); gs = wgrad ? nrt nct : nct (workgroups per group); ng = wgrad ? nsplit : nrt (groups)
+        (ng & 7) == 0: the XCD-aware remap  q = lid >> 3, member = q % gs, group = (q / gs) 8 + (lid & 7); else member = lid % gs, group = lid / gs
+        wgrad: per = round_up(ceil(ktot / nsplit), 16); split z contracts [z per, min((z + 1) per, ktot)): empty when z per >= ktot
+    Returns dict(nrt, nct, gs, ng, remap, per, empty: the number of empty splits, tiles: the (group, member) of every workgroup id)."""
+    nrt, nct = (rows + 127) // 128, (cols + 127) // 128
+    wgrad = kind == "wgrad"
+    gs, ng = (nrt * nct, nsplit) if wgrad else (nct, nrt)
+    remap = ng % 8 == 0
+    tiles = []
+    for lid in range(gs * ng):
+        q = lid >> 3
+        tiles.append(((q // gs) * 8 + (lid & 7), q % gs) if remap else (lid // gs, lid % gs))
+    per = _up((ktot + nsplit - 1) // nsplit, 16) if wgrad else 0
+    empty = sum(1 for z in range(nsplit) if z * per >= ktot) if wgrad else 0
+    return dict(nrt=nrt, nct=nct, gs=gs, ng=ng, remap=remap, per=per, empty=empty, tiles=tiles)
+
+
+def general_ray_runs(R, S, need_of_rays, budget):
+    """plan_ray_chunks of nca_api_wide.inc restated: rays per run of a backward that recomputes -- rays = min(R, 2^18 / S), halved ((rays + 1) / 2) while the
+    regions of a run of `rays` rays (need_of_rays(rays), bytes) exceed `budget` and rays > 1."""
+    rays = max(1, min(R, (1 << 18) // S))
+    while need_of_rays(rays) > budget and rays > 1:
+        rays = (rays + 1) // 2
+    return rays
 
 
 def onehot_latent_rows(tl, phase, tag):
@@ -460,6 +573,14 @@ def onehot_checks_ab(spec, params, g, x, tag, deltas_nonzero=True):
     e, at = rank_one_err(dWo, dbo)
     assert e <= 2.0 ** -20, (tag, "output_linear.0.weight", at, e)
     return max(worst, e)
+
+
+def onehot_channel_rows(dWo, dbo, o, tag):
+    """Check B on the output layer [Cout, F] of a one-hot at output channel o: every other row of dWo and entry of dbo is zero bit for bit (no
+    leakage between the output channels), and dbo[o] is the coefficient itself, exactly 1."""
+    rest = torch.arange(dbo.numel()) != o
+    assert not bool(dWo[rest].any()) and not bool(dbo[rest].any()), (tag, "B: output channels other than o*", torch.nonzero(dWo[rest])[:4].tolist())
+    assert float(dbo[o]) == 1.0, (tag, "dbo[o*]", float(dbo[o]))
 
 
 def oracle_fine_sampler(sig_s, sig_d, z, u, reduce_max=None):

@@ -1,5 +1,7 @@
 """Every entry of every parameter gradient of the fused MLP kernels (forward, dgrad sweep, weight-gradient and reduce kernels of
-nca_kernels_f32.hip / nca_kernels_bf16.hip, the point kernels and the general kernels) held to the f64 oracle -- not one number per tensor.
+nca_kernels_f32.hip / nca_kernels_bf16.hip, the point kernels) held to the f64 oracle -- not one number per tensor.  Of the general kernels
+this module reaches one launch shape (144 units, 300 points in one chunk of three row tiles and splits: identity tile order, no skip layer, one
+output channel, no ray batch); their tile, split and run seams are held in tests/test_onehot_general_gpu.py.
 
 The other gradient tests bound rel_err = max |a - b| / max |b| per tensor at 1e-5 (f32) or 5e-2 (bf16): random nets sum thousands of
 random-signed samples (cancellation hides small errors) and ReLU pre-activations within rounding of zero flip masks.  Here both causes
@@ -292,7 +294,7 @@ def test_onehot_points(dev, name, prec):
 
 
 def test_onehot_points_general_kernels(dev):
-    """The general kernels (F = 144 > 128 units; f32) on 300 points with a 3 MB workspace (128-row chunks), n* in {0, 127, 128, 299}: check A
+    """The general kernels (F = 144 > 128 units; f32) on 300 points with a 3 MB workspace (the 384 rows fit it: one chunk of three row tiles and three splits, tests/test_onehot_general_cpu.py), n* in {0, 127, 128, 299}: check A
     (the same 2^-20 of v_mfma_f32_32x32x2_f32: one product per entry), B, and C at 1e-5 -- with the f32 rule's floor, as for the fused
     kernels: without it the first layer's weights measure 4.33e-5 (row 50, column 42: the cosine of band 6), which is the f32 oracle's own
     4.3e-5 from the f64 one -- the reference forms a cosine as sin(fl32(2^k x) + fl32(pi / 2)) (oracle.encode), and so do the kernels and the

@@ -240,6 +240,70 @@ def test_general_kernels_refusals(golden, dev):
 
 
 @pytest.mark.gpu
+def test_general_kernels_refuse_depth_and_per_point_latent_gradients(dev):
+    """The two refusals test_general_kernels_refusals names and does not trigger, from Python on the nets of the one-hot case RG (144 units, both on the
+    general kernels): depth gradients of a ray batch and per-point latent gradients of Temporal.query_time are refused by name, and no gradient buffer
+    is touched -- neither the parameters' .grad through autograd nor, at the raw entry points, a byte of the buffers handed in."""
+    from nerfca_amd import _capi, fused as FZ
+    from nca_testlib import general_case, hip_render_grads, onehot_coeffs
+    c = general_case("RG")
+    s = make_static(c.ps, dev, F=c.F, early=c.early, late=c.late)
+    t = make_dynamic(c.pd, dev, F=c.Fd, early=c.early_d, late=0, T=8)
+    for m in (s, t):
+        m.update_freq_mask_alpha(75000, 150000)
+    assert _capi.net_is_general(s._binding.net) and _capi.net_is_general(t._binding.net)
+    R, S = c.o.shape[0], c.S
+    cp, cs, cd = onehot_coeffs(R, S, "s", 4, 32)
+
+    def untouched():
+        return all(p.grad is None for m in (s, t) for p in m.parameters())
+
+    # depth gradients: through autograd ...
+    with pytest.raises(_capi.NcaError, match="depth gradients need both nets on the fused kernels"):
+        hip_render_grads(s, t, dev, c.o, c.d, c.ph, c.I0, c.z, c.dists, cp, cs, cd, want_depth=True)
+    assert untouched()
+    # ... and at the raw entry point, with and without a forward store
+    bs, bd = s._binding, t._binding
+    for limit in (FZ.STORE_FORWARD_LIMIT_BYTES, 0):
+        old = FZ.STORE_FORWARD_LIMIT_BYTES
+        FZ.STORE_FORWARD_LIMIT_BYTES = limit
+        try:
+            batch = FZ._RayBatch(c.o.to(dev), c.d.to(dev), c.ph.to(dev), c.I0.to(dev), c.z.to(dev)[None, :].repeat(R, 1), c.dists.to(dev), "softplus", False, 1e-2)
+            keep = FZ.render_forward_raw(batch, bs, bd, for_backward=True)[3]
+            assert (keep[6] is not None) == (limit > 0)
+            out_s, out_d = torch.full_like(bs.flat, 7.0), torch.full_like(bd.flat, 7.0)
+            with pytest.raises(_capi.NcaError, match="depth gradients need both nets on the fused kernels"):
+                FZ.render_backward_raw(batch, bs, bd, keep, cp.to(dev), cs.to(dev), cd.to(dev), want_depth_grad=True, out_s=out_s, out_d=out_d)
+        finally:
+            FZ.STORE_FORWARD_LIMIT_BYTES = old
+        assert bool((out_s == 7.0).all()) and bool((out_d == 7.0).all())
+    # per-point latent gradients: through autograd ...
+    N = 40
+    x = c.o[:1].float().repeat(N, 1).to(dev) * 0.1
+    lat = t.time_latents.detach()[c.ph.repeat(5)[:N].to(dev)].clone().requires_grad_(True)
+    y = t.query_time(x, lat)
+    with pytest.raises(_capi.NcaError, match="per-point latent gradients of a net on the general kernels"):
+        y.sum().backward()
+    assert untouched() and lat.grad is None
+    with torch.no_grad():
+        assert bool(torch.isfinite(t.query_time(x, lat.detach())).all())          # (the forward itself runs)
+    # ... and at the raw entry point
+    lib = _capi.lib()
+    packed = bd.ensure_packed()
+    win, _ = t._enc_buffers()
+    ids = torch.zeros(N, dtype=torch.int32, device=dev)
+    g = torch.ones(N, device=dev)
+    grads, g_lat = torch.full_like(bd.flat, 7.0), torch.full((N, 8), 7.0, device=dev)
+    nbytes = lib.nca_mlp_bwd_workspace(C.byref(bd.net), bd.prec, N, 0)
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rc = lib.nca_mlp_bwd(C.byref(bd.net), bd.prec, packed.data_ptr(), win.data_ptr(), None, bd.flat.data_ptr(), N, x.contiguous().data_ptr(), ids.data_ptr(),
+                         g.data_ptr(), grads.data_ptr(), g_lat.data_ptr(), work.data_ptr(), nbytes, None)
+    torch.cuda.synchronize(dev)
+    assert rc == -2 and b"per-point latent gradients of a net on the general kernels" in lib.nca_last_error()
+    assert bool((grads == 7.0).all()) and bool((g_lat == 7.0).all())
+
+
+@pytest.mark.gpu
 def test_trainer_steps_with_wide_nets(dev):
     """CompositeTrainer over nets of 136 units (general kernels, width 144): the autograd step, the fused step and the graph-replayed step all
     train, agree on the first step's loss, the loss falls, and the padding units stay at zero."""
