@@ -1065,6 +1065,66 @@ int nca_vol_vesselness(const NcaGrid* grid, const float* s, int32_t n_vol, doubl
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_vess_last_error(void);
 
+/* ---- mesh: the iso-surfaces of voxel stacks as indexed triangle meshes (mesh.isosurface / export.density_surfaces) ---------------------------
+ * Marching tetrahedra on the Kuhn (Freudenthal) split of every grid cell: a 16-case table, no ambiguous case, and a split that is the same in
+ * every cell and agrees across cell faces, so the mesh is an oriented closed 2-manifold wherever the surface does not touch a face of the
+ * grid.  Purely additive to ABI 13.  Like the other view sections these entry points keep their OWN per-thread message (the accessor below);
+ * a refused call launches nothing and reads no device pointer; a launch failure is reported once.  vol is f32 [n_vol][n0][n1][n2] contiguous
+ * on the device, on one NcaGrid (`grid` is a host pointer); level is a finite f32.  Every volume is meshed on its own: its result does not
+ * depend on n_vol or on its neighbours in the stack, and its vertex indices start at 0.  Every f64 operation below is ONE rounded operation
+ * in the order written (no fused multiply-add anywhere), so a transcription into any IEEE arithmetic has the same bits.
+ *
+ * INSIDE.  Node j is inside iff vol[j] > level as f32: a NaN and a value equal to the level are not.
+ * EDGES.  Node i = (i0, i1, i2), linear index (i0 n1 + i1) n2 + i2, OWNS the edges k = 1 .. 7 to i + d_k, d_k = ((k >> 2) & 1, (k >> 1) & 1,
+ *     k & 1), whose far end is a node of the grid.  An edge whose ends differ in "inside" is CROSSED and carries exactly one vertex.
+ * VERTICES.  With a the owning end, b the far end and v_a, v_b their values taken to f64:
+ *     t = ((double)level - v_a) / (v_b - v_a);   t = 0.5 if that is not finite, else min(max(t, 0), 1);
+ *     q_x = (double)i_x + t on the axes x with d_x = 1, (double)i_x on the others;   h_x = 1 / inv_x;   vertex_x = (float)(lo_x + q_x * h_x).
+ *     The vertices of a volume are numbered by (linear index of the owning node, k) ascending: no vertex twice, no gaps.
+ * NORMALS (optional), per vertex.  G_x(i) = (0.5 * ((double)vol[i + e_x] - (double)vol[i - e_x])) * inv_x with both indices clamped to
+ *     [0, n_x - 1] (edge replication, as in "vess");   m_x = -(G_x(a) + t * (G_x(b) - G_x(a)));   len = sqrt((m_0 m_0 + m_1 m_1) + m_2 m_2);
+ *     normal_x = (float)(m_x / len), or (+0, +0, +0) where len is 0 or not finite.  It points to the outside (down the values).
+ * CELLS.  Every node c with c_x + 1 < n_x on all three axes is the base of a cell, numbered by c's linear index.  A cell has six tetrahedra
+ *     q = 0 .. 5, one per permutation (a, b, c') of the axes in the order (0,1,2), (0,2,1), (1,0,2), (1,2,0), (2,0,1), (2,1,0), with the corners
+ *     p0 = c, p1 = p0 + e_a, p2 = p1 + e_b, p3 = p2 + e_c' = c + (1,1,1).  Tetrahedra 1, 2 and 5 (the odd permutations) are mirror images.
+ * TRIANGLES.  The edges of a tetrahedron are numbered 0 .. 5 = (p0 p1), (p0 p2), (p0 p3), (p1 p2), (p1 p3), (p2 p3); each is the edge k = the
+ *     difference of its ends, owned by its lower end.  With case = sum over the corners p_i inside of 2^i, the triangles are, as edge numbers:
+ *         1: 0 1 2      2: 0 4 3      4: 1 3 5      8: 2 5 4       7: 2 4 5      11: 1 5 3      13: 0 3 4      14: 0 2 1
+ *         3: 1 2 4, 1 4 3      5: 0 3 5, 0 5 2      6: 0 4 5, 0 5 1      9: 0 1 5, 0 5 4      10: 0 2 5, 0 5 3      12: 1 3 4, 1 4 2
+ *     (cases 0 and 15: none; two corners inside: the quadrilateral is split along the diagonal from its lowest-numbered edge).  In an odd
+ *     tetrahedron the second and third vertex of every triangle change places.  Every triangle is counter-clockwise seen from the outside,
+ *     so the divergence-theorem volume of a bright blob is positive.  The triangles of a volume are ordered by (cell, tetrahedron, position
+ *     in the list above); a triangle is three vertex numbers of its volume, int32.  Triangles of zero area (a node exactly at the level gives
+ *     t = 0 or 1) are kept: the combinatorics stay those of a manifold.
+ *
+ * nca_vol_iso_count: totals int64 [n_vol][2] on the device = (vertices, triangles) of every volume, and in the workspace every node's first
+ *     vertex and first triangle within its volume and every volume's first of both in the stack.  Five launches: per tile of 4 x 8 x 64 nodes,
+ *     staged with the next node on every axis in LDS (5 x 9 x 65 f32), every node's crossing mask and its cell's triangle count as one 16-bit
+ *     word; then an exclusive scan per volume in three steps -- the sums of every 1024 consecutive nodes, their scan by one workgroup per
+ *     volume (and one workgroup for the stack), and the scan within every 1024 nodes plus that offset.  Offsets within a volume are int32:
+ *     a grid with 7 n0 n1 n2 or 12 (n0 - 1)(n1 - 1)(n2 - 1) above 2^31 - 1 is refused.
+ * nca_vol_iso_emit: after nca_vol_iso_count on the same arguments and workspace, and after the caller has read totals to size the outputs:
+ *     verts f32 [sum V][3], tris int32 [sum T][3], normals f32 [sum V][3] or NULL, the volumes back to back in stack order.  One launch over
+ *     the same tiles; every vertex and triangle is written once, by the thread that owns it.  A store is made only below vert_cap vertices
+ *     and tri_cap triangles, whatever the workspace holds; verts (and normals) may be NULL when vert_cap is 0, tris when tri_cap is 0, and
+ *     with both 0 nothing is launched.
+ * No atomics, no workgroup waits for another: the same bits on every run.  The tiling sets no limit on an axis.
+ * The workspace, with s = n0 n1 n2 rounded up to a multiple of 4 and round256 as in "label":
+ *     round256(2 n_vol s) + 2 round256(4 n_vol s) + round256(8 n_vol ceil(n0 n1 n2 / 1024)) + 2 round256(16 n_vol) bytes.
+ * The query returns it, and 0 for arguments the entry points refuse.
+ * NCA_E_INVALID (the message names the value): a NULL grid, vol or totals; a negative capacity; NULL verts or tris with a positive capacity;
+ * n_vol <= 0; the grid refusals of nca_drr_project; a level that is not finite; more than 2^31 - 1 tiles of 4 x 8 x 64 nodes or runs of 1024
+ * nodes in the stack (what one launch covers).
+ * NCA_E_UNSUPPORTED: a grid whose worst case overflows the int32 offsets.   NCA_E_WORKSPACE: work is NULL or work_bytes is below the query's
+ * answer.  The order: pointers and capacities, n_vol, the grid, the offsets, the level, the workspace, the launch limits. */
+size_t nca_vol_iso_workspace(const NcaGrid* grid, int32_t n_vol);
+int nca_vol_iso_count(const NcaGrid* grid, const float* vol, int32_t n_vol, float level, int64_t* totals, void* work, size_t work_bytes, void* stream);
+int nca_vol_iso_emit(const NcaGrid* grid, const float* vol, int32_t n_vol, float level, const void* work, size_t work_bytes, int64_t vert_cap, int64_t tri_cap,
+                     float* verts, int32_t* tris, float* normals, void* stream);
+
+/* The message of the calling thread's last failed call of this section. */
+const char* nca_mesh_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

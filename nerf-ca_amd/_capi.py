@@ -253,6 +253,10 @@ SYMBOLS = {
     "nca_vol_label": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, _I32, _I32, _P, _P, _P, C.c_size_t, _P]),
     "nca_vol_label_sizes": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, _I32, _P, _P]),
     "nca_label_last_error": (C.c_char_p, []),
+    "nca_vol_iso_workspace": (C.c_size_t, [C.POINTER(NcaGrid), _I32]),          # ("mesh": the header's last section; this table's order is not the header's)
+    "nca_vol_iso_count": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_float, _P, _P, C.c_size_t, _P]),
+    "nca_vol_iso_emit": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_float, _P, C.c_size_t, _I64, _I64, _P, _P, _P, _P]),
+    "nca_mesh_last_error": (C.c_char_p, []),
     "nca_vol_hessian_eig": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, _P, _P]),
     "nca_vol_hessian_norm_max": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, _P, _P]),
     "nca_vol_vesselness": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, C.c_double, C.c_double, _P, _I32, _I32, _P, _P, _P]),
@@ -305,6 +309,7 @@ check_filt = _section_check("nca_filt_last_error", "filter entry points (nca_vol
 check_resample = _section_check("nca_resample_last_error", "resampling entry points (nca_vol_spline_filter, nca_vol_zoom*)")
 check_skel = _section_check("nca_skel_last_error", "soft-skeleton entry points (nca_vol_softskel*, nca_vol_overlap_sums*)")
 check_label = _section_check("nca_label_last_error", "connected-component entry points (nca_vol_label*)")
+check_mesh = _section_check("nca_mesh_last_error", "iso-surface entry points (nca_vol_iso_*)")
 check_vess = _section_check("nca_vess_last_error", "vesselness entry points (nca_vol_hessian_*, nca_vol_vesselness)")
 
 

@@ -20,6 +20,7 @@ import torch
 from . import _capi
 from . import _view
 from . import fused as _fused
+from . import mesh as _mesh
 from .fused import eval_points
 
 
@@ -112,6 +113,24 @@ def density_volumes(static_model, temp_model, phases: Sequence[int], resolution:
                 out_d[j, i:i + n] = sigma(eval_points(temp_model, pts, ph.fill_(phase)), n)
     shape = tuple(int(n) for n in resolution)
     return out_s.reshape(shape), (out_d.reshape((len(phases),) + shape) if out_d is not None else None)
+
+
+@torch.no_grad()
+def density_surfaces(static_model, temp_model, phases: Sequence[int], level: float, resolution: Sequence[int] = (128, 128, 128),
+                     bounds: Tuple[Tuple[float, float], ...] = ((-1.0, 1.0), (-1.0, 1.0), (-1.0, 1.0)), output_activation: str = "softplus",
+                     scale_value: float = 1e-2, chunk_points: int = 1 << 22, *, field: str = "dynamic", normals: bool = False) -> "List[_mesh.Mesh]":
+    """The 4-D reconstruction as surfaces: one ``mesh.Mesh`` per heart phase of ``phases``, the iso-surface at ``level`` of the density
+    sampled by ``density_volumes`` (same arguments) -- of the dynamic field (``field="dynamic"``, the vessels), of the sum of both fields
+    (``"total"``), or, as a list of one, of the static field (``"static"``; ``temp_model`` may then be None).  Vertices are in the
+    coordinates of ``bounds``.  One ``density_volumes`` and one ``mesh.isosurface`` over the stack: one host read in all."""
+    who = "density_surfaces"
+    if field not in ("dynamic", "total", "static"):
+        raise _capi.NcaError(f"{who}: field = {field!r} is not 'dynamic', 'total' or 'static'")
+    if field != "static" and temp_model is None:
+        raise _capi.NcaError(f"{who}: field = {field!r} needs the dynamic model")
+    sig_s, sig_d = density_volumes(static_model, temp_model if field != "static" else None, phases, resolution, bounds, output_activation, scale_value, chunk_points)
+    stack = sig_s[None] if field == "static" else (sig_d if field == "dynamic" else sig_d + sig_s[None])
+    return _mesh.isosurface(stack, level, bounds, normals=normals)
 
 
 # ----------------------------------------------------------------------------- view rendering
