@@ -194,7 +194,10 @@ int nca_render_fwd(const NcaRays* rays, int32_t prec,
  * (rays->store_format = that forward's return value).
  * Upstream gradients g_pix f64[R], g_sig_s/g_sig_d f32[R,S] (NULL = 0).
  * Writes (overwrites) grads_s / grads_d, flat f32 in the natural parameter order.
- * `params_*` are the natural flat parameters (needed for the latent gradient). */
+ * `params_*` are the natural flat parameters (needed for the latent gradient).
+ * max_bytes: the cap the caller can afford.  With a net on the general kernels max_bytes <= 0 is NOT "no cap" but the smallest plan (one ray per run);
+ * a backward from the general forward store (NCA_STORE_GENERAL) takes the scratch of all its rays at once and refuses a workspace sized that way
+ * with NCA_E_WORKSPACE: pass a real cap (fused.py: at least 1 MiB). */
 int64_t nca_render_bwd_workspace(const NcaRays* rays, const NcaNet* net_s, const NcaNet* net_d, int32_t prec,
                                  int64_t max_bytes);
 int nca_render_bwd(const NcaRays* rays, int32_t prec,
@@ -992,7 +995,7 @@ int nca_vol_label(const NcaGrid* grid, const float* vol, int32_t n_vol, double t
 
 /* COMPONENT SIZES.  labels int32 [n_vol][n0][n1][n2] on the device (any labels, nca_vol_label's or not); sizes int32 [n_vol][cap] on the device:
  *     sizes[v cap + l] = the number of nodes of volume v whose label is l, for 0 <= l < cap: entry 0 is the background.
- * A label outside [0, cap) is not counted.  The entry point zeroes `sizes` itself (a memset on the stream), then one launch: runs of equal
+ * A label outside [0, cap) is not counted.  The entry point zeroes `sizes` itself (a fill kernel on the stream: a captured call replays), then one launch: runs of equal
  * labels are merged within a wave, then per workgroup of 4096 nodes in a table of 256 slots in LDS, and every slot is one integer atomicAdd
  * -- exact in any order, the same bits on every run.  No workspace.
  * NCA_E_INVALID: a NULL grid, labels or sizes; n_vol <= 0; cap <= 0; the grid refusals of nca_drr_project; more than 2^24 workgroups.
@@ -1043,14 +1046,14 @@ const char* nca_label_last_error(void);
  * nca_vol_hessian_norm_max: norm_max f64 [n_vol] on the device, norm_max[v] = max(+0, the maximum over the nodes of volume v of
  *     S2' = (x1 * x1 + x2 * x2) + x3 * x3,  x_j = l_j rounded to f32 and taken back to f64) -- the S2 of what nca_vol_hessian_eig writes, so
  *     a caller can form the same number from eig.  max(a, b) = (b > a) ? b : a: a NaN is passed over, +inf is kept.  The entry point zeroes
- *     norm_max itself (a memset on the stream); a workgroup takes the maximum of its tile in a tree and makes one integer atomicMax on the
+ *     norm_max itself (a fill kernel on the stream: a captured call replays); a workgroup takes the maximum of its tile in a tree and makes one integer atomicMax on the
  *     bit pattern, which orders non-negative doubles as their values do: exact in any order, the same bits on every run.  Frangi's rule is
  *     c = 0.5 sqrt(norm_max).
  * nca_vol_vesselness: out f32 [n_vol][n0][n1][n2], scale_out int32 of the same shape or NULL.  scale_index == 0: every node of out is
  *     written with V and every node of scale_out with 0.  scale_index > 0: out and scale_out are read-modify-write, a node is replaced by
  *     (V, scale_index) only where V > out (the f32 values): over increasing scale_index the result is the maximum over the scales and the
  *     SMALLEST index that attains it.
- * One launch each (norm_max: a memset before it).  A workgroup owns a tile of 4 x 8 x 64 nodes, stages it with a halo of one node in LDS
+ * One launch each (norm_max: the fill kernel before it).  A workgroup owns a tile of 4 x 8 x 64 nodes, stages it with a halo of one node in LDS
  * (6 x 10 x 66 f32), and each thread forms the 19-point stencil of its four nodes and runs the solver in registers.  Every node is written
  * once by the thread that owns it.  No workspace.  The tiling sets no limit on an axis.  No output may be s itself (refused; an overlap is
  * not detected).

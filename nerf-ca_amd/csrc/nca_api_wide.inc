@@ -223,7 +223,7 @@ static int wide_backward(const WideBind& w, const NcaWideGeom& geom, int64_t N, 
     wide_plan(y, N, true, work_bytes, &p);
     if (!work || p.bytes > work_bytes) return fail(NCA_E_WORKSPACE, "general kernels: backward workspace %lld < %lld bytes", (long long)work_bytes, (long long)p.bytes);
     float* ws = static_cast<float*>(work);
-    HIPCHK(hipMemsetAsync(grads, 0, (size_t)y.n_params * 4, st));
+    HIPCHK(nca_launch_wide_zero(grads, y.n_params, st));          // (a kernel, not hipMemsetAsync: nca_wide.hpp)
     for (int64_t n0 = 0; n0 < N; n0 += p.chunk) {
         const int64_t n_valid = N - n0 < p.chunk ? N - n0 : p.chunk;
         const int64_t rows = align_up(n_valid, NCA_WIDE_ROWS);
@@ -374,7 +374,7 @@ static int render_fwd_general(const NcaRays* rays, int32_t prec, const NetBind* 
         }
         // the raw fields stay in the store's tail for the backward's compositing chain rule; the sigma buffers become sigmas in place
         for (int n = 0; n < nn; ++n)
-            HIPCHK(hipMemcpyAsync(sb + gs.raw_off + (int64_t)n * rays->R * S, outs[n], (size_t)rays->R * S * 4, hipMemcpyDeviceToDevice, st));
+            HIPCHK(nca_launch_wide_copy(sb + gs.raw_off + (int64_t)n * rays->R * S, outs[n], rays->R * S, st));
         int rc = nca_composite_fwd(rays->R, rays->S, rays->act, rays->single_field, rays->scale, sig_s, nn == 2 ? sig_d : nullptr, rays->I0, rays->dists, pix, sig_s,
                                    nn == 2 ? sig_d : nullptr, (void*)st);
         return rc ? rc : NCA_STORE_GENERAL;
@@ -453,7 +453,7 @@ static int render_bwd_general(const NcaRays* rays, int32_t prec, const NetBind* 
             int rc = wide_bind(binds[n], prec, &wb[n]);
             if (rc) return rc;
             lays[n] = wb[n].y;
-            HIPCHK(hipMemsetAsync(grads[n], 0, (size_t)wb[n].y.n_params * 4, st));
+            HIPCHK(nca_launch_wide_zero(grads[n], wb[n].y.n_params, st));
         }
         GeneralStore gs;
         if (!general_store_plan(lays, nn, rays->R, rays->S, &gs) || store_bytes < gs.bytes)
@@ -507,7 +507,7 @@ static int render_bwd_general(const NcaRays* rays, int32_t prec, const NetBind* 
             if (wb[n].y.C != 3 || wb[n].y.Cout != 1) return fail(NCA_E_UNSUPPORTED, "a ray batch needs nets with 3 input channels and 1 output channel");
             if (wb[n].y.T > 0 && !rays->phase) return fail(NCA_E_INVALID, "dynamic net needs phase ids");
             lays[n] = wb[n].y;
-            HIPCHK(hipMemsetAsync(grads[n], 0, (size_t)wb[n].y.n_params * 4, st));
+            HIPCHK(nca_launch_wide_zero(grads[n], wb[n].y.n_params, st));
         } else {
             rc = fused_raw_forward(rays, prec, binds[n], raw[n], st);
             if (rc) return rc;

@@ -485,3 +485,23 @@ hipError_t nca_launch_wide_reduce(const NcaWideReduceArgs& a, hipStream_t st) {
     }
     return e;
 }
+
+// ------------------------------------------------------------------------------------------ clear, copy
+__global__ __launch_bounds__(256) void nca_wide_zero(float* __restrict__ p, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = 0.f;
+}
+__global__ __launch_bounds__(256) void nca_wide_copy(float* __restrict__ dst, const float* __restrict__ src, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) dst[i] = src[i];
+}
+hipError_t nca_launch_wide_zero(float* p, int64_t n, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    const int64_t nb = (n + 255) / 256;
+    hipLaunchKernelGGL(nca_wide_zero, dim3((unsigned)(nb < 65536 ? nb : 65536)), dim3(256), 0, st, p, n);
+    return hipGetLastError();
+}
+hipError_t nca_launch_wide_copy(float* dst, const float* src, int64_t n, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    const int64_t nb = (n + 255) / 256;
+    hipLaunchKernelGGL(nca_wide_copy, dim3((unsigned)(nb < 65536 ? nb : 65536)), dim3(256), 0, st, dst, src, n);
+    return hipGetLastError();
+}

@@ -140,3 +140,8 @@ struct NcaWideReduceArgs {
     float* esum;                  // [F][P] scratch: per-phase sums of D_0 (T > 0)
 };
 hipError_t nca_launch_wide_reduce(const NcaWideReduceArgs& a, hipStream_t st);
+
+// p[0 .. n) = +0.0f and dst[0 .. n) = src[0 .. n), as KERNELS: the library issues no hipMemset* / hipMemcpy* -- a memset node captured into a HIP graph does not
+// replay to what the eager call does (docs/DESIGN_rounds1-4.md 4.4; tests/test_graph_replay_gpu.py), kernel nodes do
+hipError_t nca_launch_wide_zero(float* p, int64_t n, hipStream_t st);
+hipError_t nca_launch_wide_copy(float* dst, const float* src, int64_t n, hipStream_t st);

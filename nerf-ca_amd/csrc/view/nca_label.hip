@@ -423,6 +423,10 @@ __global__ void __launch_bounds__(SZ_BLOCK) label_sizes_kernel(int64_t voxels, i
     if (s_key[tid] >= 0) atomicAdd(out + s_key[tid], s_cnt[tid]);
 }
 
+__global__ void label_zero_kernel(int32_t* __restrict__ p, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = 0;
+}
+
 extern "C" int nca_vol_label_sizes(const NcaGrid* grid, const int32_t* labels, int32_t n_vol, int32_t cap, int32_t* sizes, void* stream) {
     const char* who = "nca_vol_label_sizes";
     NCA_REFUSE_NULL_GRID(g_err, who, grid);
@@ -437,8 +441,12 @@ extern "C" int nca_vol_label_sizes(const NcaGrid* grid, const int32_t* labels, i
     const int rcb = nca_check_launch_blocks(g_err, who, n_vol, g, chunks * n_vol, 0, 0, SZ_MAX_BLOCKS);
     if (rcb != NCA_OK) return rcb;
     hipStream_t s = (hipStream_t)stream;
-    const hipError_t e = hipMemsetAsync(sizes, 0, (size_t)n_vol * (size_t)cap * sizeof(int32_t), s);
-    if (e != hipSuccess) return g_err.fail(NCA_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    // the clear is a KERNEL on the stream, not hipMemsetAsync: a memset node captured into a HIP graph does not replay to what the eager call does
+    // (tests/test_graph_replay_gpu.py: the sizes came back on top of what the buffer held)
+    const int64_t n_sizes = (int64_t)n_vol * cap, zb = (n_sizes + SZ_BLOCK - 1) / SZ_BLOCK;
+    hipLaunchKernelGGL(label_zero_kernel, dim3((unsigned)(zb < 65536 ? zb : 65536)), dim3(SZ_BLOCK), 0, s, sizes, n_sizes);
+    const int rcz = nca_launched(g_err, who);
+    if (rcz != NCA_OK) return rcz;
     hipLaunchKernelGGL(label_sizes_kernel, dim3((unsigned)(chunks * n_vol)), dim3(SZ_BLOCK), 0, s, voxels, chunks, cap, labels, sizes);
     return nca_launched(g_err, who);
 }

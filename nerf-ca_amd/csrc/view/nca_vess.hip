@@ -202,6 +202,11 @@ extern "C" int nca_vol_hessian_eig(const NcaGrid* grid, const float* s, int32_t 
     return nca_launched(g_err, who);
 }
 
+__global__ __launch_bounds__(256) void vess_zero_kernel(unsigned long long* __restrict__ p, int32_t n) {
+    const int32_t i = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+    if (i < n) p[i] = 0ull;
+}
+
 extern "C" int nca_vol_hessian_norm_max(const NcaGrid* grid, const float* s, int32_t n_vol, double scale, double* norm_max, void* stream) {
     const char* who = "nca_vol_hessian_norm_max";
     NCA_REFUSE_NULL_GRID(g_err, who, grid);
@@ -215,8 +220,11 @@ extern "C" int nca_vol_hessian_norm_max(const NcaGrid* grid, const float* s, int
     if (rc != NCA_OK) return rc;
     rc = vess_blocks(who, g, n_vol, nb, &tiles);
     if (rc != NCA_OK) return rc;
-    const hipError_t e = hipMemsetAsync(norm_max, 0, sizeof(double) * (size_t)n_vol, (hipStream_t)stream);          // +0.0 is all zero bits
-    if (e != hipSuccess) return g_err.fail(NCA_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    // the clear is a KERNEL on the stream, not hipMemsetAsync: a memset node captured into a HIP graph does not replay to what the eager call does
+    // (tests/test_graph_replay_gpu.py), and a stale maximum would survive into every later replay on a dimmer volume
+    hipLaunchKernelGGL(vess_zero_kernel, dim3((unsigned)((n_vol + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (unsigned long long*)norm_max, n_vol);          // +0.0 is all zero bits
+    rc = nca_launched(g_err, who);
+    if (rc != NCA_OK) return rc;
     hipLaunchKernelGGL((vess_kernel<VS_NORM>), dim3((unsigned)(tiles * n_vol)), dim3(NCA_TILE_BLOCK), 0, (hipStream_t)stream, g.n[0], g.n[1], g.n[2], nodes / n_vol, tiles,
                        nb[1], nb[2], s, scale, (float*)nullptr, (int32_t*)nullptr, (unsigned long long*)norm_max, (const double*)nullptr, 0.0, 0.0, 0, 0);
     return nca_launched(g_err, who);

@@ -723,3 +723,141 @@ def gpu_stack_call(dev, check, fn, query, g, vol, args, fill, dtype, node_bytes,
         check(fn(C.byref(g), _capi.ptr(x), n_vol, *args, _capi.ptr(out), _capi.ptr(work), nbytes, fused._stream()))
     torch.cuda.synchronize(dev)
     return out.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------ graph replay: the input sequences of both halves
+# (tests/test_graph_replay_gpu.py replays every captured entry point on these inputs in this order; tests/test_graph_replay_cpu.py proves with
+# the numpy references that a clear which did nothing under replay -- a running maximum, a running sum -- would show on every replay after the
+# first.)  The order makes stale state visible: the amplitudes fall, so every maximum falls strictly; the threshold stays, so the mask shrinks
+# and the components change; every sum moves by far more than its tolerance.
+REPLAY_INPUTS = 3                      # inputs per case; the last one is replayed twice
+REPLAY_AMPLITUDES = (1.0, 0.7, 0.45)
+REPLAY_THRESHOLD = 0.3                 # of the label, edt, city-block and iso-surface cases: 70 %, 57 % and 33 % of the nodes lie above it
+REPLAY_TILE_SHAPE = (5, 9, 65)         # one node past the 4 x 8 x 64 tile on every axis
+REPLAY_LINE_SHAPE = (3, 5, 65)         # edt and filt: one node past a chunk of 64
+REPLAY_ZOOM = ((3, 5, 70), (6, 5, 33))
+REPLAY_DRR_SHAPE = (5, 3, 4)
+REPLAY_SSIM = (11, (27, 43))           # window 11: 17 x 33 positions, one row and one column past the 16 x 32 tile
+REPLAY_VESS_SCALE = 2.25
+REPLAY_VESS_SIGMAS = (1.0, 1.5)
+REPLAY_LABEL_CAP = 64
+REPLAY_MLP = ("F144_e1", 300)          # the one-hot module's general-kernel point case
+REPLAY_RAYS = (7, 40)                  # R, S of the render case: both nets general (144 units)
+
+
+def replay_volumes(shape, k, n_vol=2):
+    """Input k of a volume case: f32 [n_vol, n0, n1, n2], uniform in [0, REPLAY_AMPLITUDES[k]); the volumes of a stack differ."""
+    rng = np.random.default_rng(4100 + 10 * k + 7 * shape[0] + 3 * shape[1] + shape[2])
+    return (rng.random((n_vol,) + tuple(shape)) * REPLAY_AMPLITUDES[k]).astype(np.float32)
+
+
+def replay_images(k):
+    """Input k of the ssim cases: (x, y, range) with x, y f32 [2, H, W] and range f64 [2].  The truth y stays; the prediction x is y under noise
+    that grows with k, so every image's sum of S falls by tens from input to input."""
+    H, W = REPLAY_SSIM[1]
+    y = np.random.default_rng(4200).random((2, H, W)).astype(np.float32)
+    noise = np.random.default_rng(4201 + k).random((2, H, W)) - 0.5
+    x = np.clip(y + (0.05, 0.3, 0.9)[k] * noise, 0.0, 1.0).astype(np.float32)
+    return x, y, np.array([1.0, 1.0])
+
+
+def replay_drr_rays():
+    """(o f64 [64, 3], d f64 [64, 3], z f32 [16], dists f64 [16]): the 8 x 8 detector of the drr tests, from the host geometry."""
+    import drr_ref
+    _, geo, S = drr_ref.geometries()[0]
+    o, d = drr_ref.host_rays(geo, *drr_ref.VIEWS[0])
+    z, dists = drr_ref.depths(geo, S)
+    return o, d, z, dists
+
+
+def replay_pixel_gradients(k, R):
+    """Input k of the back-projection case: g_pix f64 [2, R], its size falling with REPLAY_AMPLITUDES."""
+    return np.random.default_rng(4300 + k).standard_normal((2, R)) * REPLAY_AMPLITUDES[k]
+
+
+def replay_upstream(k, shape):
+    """Input k of the general kernels' cases: an upstream gradient f32 of `shape`."""
+    return torch.randn(shape, generator=torch.Generator().manual_seed(4400 + k)) * REPLAY_AMPLITUDES[k]
+
+
+def replay_phantom_tables(k, P=2, n_ell=3, n_seg=7):
+    """Input k of the phantom case: (ell f64 [P, n_ell, 14], seg f64 [P, n_seg, 8])."""
+    import phantom_ref
+    return (phantom_ref.random_ellipsoids(P, n_ell, phantom_ref.BOUNDS, seed=4500 + k),
+            phantom_ref.random_segments(P, n_seg, phantom_ref.BOUNDS, seed=4600 + k, r_max=0.35))
+
+
+# The tolerances of the outputs summed with floating-point atomics, restated from the GPU tests of their sections (no new number): both halves
+# of the replay tests take them from here.
+def replay_ssim_tol(want):
+    """tests/test_ssim_gpu.py sum_bound: f64 [N] from ssim_ref.ssim_stack's dict."""
+    return 2 * want["count"] * 2.0 ** -53 * want["abs_sum"] + 4 * 2.0 ** -52 * want["abs_sum"]
+
+
+def replay_voltv_tol(want):
+    """tests/test_voltv_gpu.py value_bounds: (space, time) from voltv_ref.total_variation's dict."""
+    return np.array([2 * want["count_space"] * 2.0 ** -53 * want["abs_space"], 2 * want["count_time"] * 2.0 ** -53 * want["abs_time"]])
+
+
+def replay_drr_tol(mass, count):
+    """tests/test_drr_grad_gpu.py: count 2^-53 mass per node, from drr_adjoint_ref.backproject's mass [n_vol, ...] and count [...]."""
+    return count[None] * 2.0 ** -53 * mass
+
+
+def replay_references():
+    """The numpy references of the accumulating outputs over the input sequences, computed once: a dict of lists over the inputs
+    norm_max f64 [2]; sizes int32 [2, cap] and counts; ssim (sum [2], tol [2]); voltv (values [2], tol [2]); drr (g_vol, tol) [2, voxels]."""
+    return _replay_references()
+
+
+@functools.lru_cache(maxsize=None)
+def _replay_references():
+    import drr_adjoint_ref
+    import drr_ref
+    import label_ref
+    import ssim_ref
+    import vess_ref
+    import voltv_ref
+    out = dict(norm_max=[], sizes=[], counts=[], ssim=[], voltv=[], drr=[])
+    o, d, z, dists = replay_drr_rays()
+    for k in range(REPLAY_INPUTS):
+        vol = replay_volumes(REPLAY_TILE_SHAPE, k)
+        out["norm_max"].append(vess_ref.norm_max(vol, REPLAY_VESS_SCALE))
+        labels, counts = label_ref.label(vol, REPLAY_THRESHOLD, 1)
+        out["sizes"].append(label_ref.sizes(labels, REPLAY_LABEL_CAP))
+        out["counts"].append(counts)
+        x, y, rng = replay_images(k)
+        w = ssim_ref.ssim_stack(x, y, rng, ssim_ref.gaussian(REPLAY_SSIM[0]))
+        out["ssim"].append((w["sum"], replay_ssim_tol(w)))
+        w = voltv_ref.total_variation(vol, voltv_ref.grid_inv(REPLAY_TILE_SHAPE, drr_ref.BOUNDS), voltv_ref.EPS_S, voltv_ref.EPS_T, True)
+        out["voltv"].append((np.array([w["space"], w["time"]]), replay_voltv_tol(w)))
+        g_vol, mass, count = drr_adjoint_ref.backproject(REPLAY_DRR_SHAPE, 2, o, d, z, dists, replay_pixel_gradients(k, o.shape[0]), drr_ref.BOUNDS)
+        out["drr"].append((g_vol.reshape(2, -1), replay_drr_tol(mass.reshape(2, -1), count.reshape(-1))))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def replay_mlp_case():
+    """The general kernels' point case: (spec, parameters, points f32 [300, 3], band window) of a static net of 144 units."""
+    F, early, late = ONEHOT_POINT_NETS[REPLAY_MLP[0]]
+    gen = torch.Generator().manual_seed(4700)
+    spec = spec_from(F, early, late)
+    return spec, O.init_params(spec, gen), torch.rand(REPLAY_MLP[1], 3, generator=gen) * 2 - 1, O.freq_mask_alpha(12, 75000, 150000, 1)[0]
+
+
+@functools.lru_cache(maxsize=None)
+def replay_ray_case():
+    """The general kernels' ray case, both nets of 144 units at R, S = REPLAY_RAYS: dict(ss, sd, ps, pd, win, o, d, ph, z, dists, I0) on the CPU."""
+    R, S = REPLAY_RAYS
+    gen = torch.Generator().manual_seed(4800)
+    ss, sd = spec_from(144, 1, 0), spec_from(144, 1, 0, T=8)
+    ps, pd = O.init_params(ss, gen), O.init_params(sd, gen)
+    o, d, ph, z, I0 = ray_inputs(R, S, gen)[:5]
+    return dict(ss=ss, sd=sd, ps=ps, pd=pd, win=O.freq_mask_alpha(12, 75000, 150000, 1)[0], o=o, d=d, ph=ph, z=z, dists=O.ray_dists(z, torch.float64), I0=I0)
+
+
+def replay_ray_upstream(k):
+    """Input k of the ray case: (g_pix f64 [R], g_sigma_s f32 [R, S], g_sigma_d f32 [R, S])."""
+    R, S = REPLAY_RAYS
+    g = replay_upstream(k, (2 * S + 1, R))
+    return g[0].double().contiguous(), g[1:S + 1].t().contiguous(), g[S + 1:].t().contiguous()

@@ -13,6 +13,13 @@ the split counts, hence the summation order; the loss, Adam, sampler and composi
 fused kernels) and the Python that drives a run (trainer.py, fused.py, schedules.py, synthetic.py, psnr_run.py): comments and layout of the
 C sources are ignored.  A test run on other sources FAILS (tests/test_psnr_gates.py, tests/test_host_cpu.py): re-take the controls.
 
+Re-taking means all of them.  The one exception on record (profiles/graph_replay.txt): a change whose new lines no control can reach -- there, clears of
+the GENERAL kernels, which run only for nets wider than 128 units while every control trains 128-unit nets on the fused kernels -- may carry
+entries over when (a) every batch size and every variant is taken again on the new sources for at least one seed and ends where the record says to
+the last digit, (b) the record of those runs is committed and given to this tool beside the old one, and (c) the commit says which entries were
+carried over and why.  The gates' two live spot checks then run on the new sources like every session.  A change to the fused f32, loss, Adam,
+sampler or compositing kernels, to the planner, or to the hashed Python never qualifies.
+
 One thing in those files is NOT hashed: the code of the static-only loop (train/run_nerf.py: StaticTrainer's fused steps, fused.static_losses,
 nca_static_loss_*), which sits in the same files between the marker comments `>>> static-only loop` and `<<< static-only loop`.  It renders one
 net with a loss of its own and is called by nothing on the composite path these controls were taken on (psnr_run.py drives CompositeTrainer), so
