@@ -1128,6 +1128,65 @@ int nca_vol_iso_emit(const NcaGrid* grid, const float* vol, int32_t n_vol, float
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_mesh_last_error(void);
 
+/* ---- path: geodesic distances under a cost, predecessors, traced paths and ball cover (centreline.geodesic_distance / extract) ---------------
+ * Minimal paths on the grid graph of a voxel stack: what the TEASAR centreline loop of centreline.extract runs on.  Purely additive to ABI 13.
+ * Like the other view sections these entry points keep their OWN per-thread message (the accessor below); a refused call launches nothing
+ * and reads no device pointer; a launch failure is reported once.  Every entry point launches on `stream` and nothing else and reads nothing
+ * back.  Every f64 operation below is ONE rounded operation in the order written (no fused multiply-add anywhere: D[u] + w must not be
+ * fused), so a transcription into any IEEE arithmetic has the same bits.
+ *
+ * GRID.  An NcaGrid, checked as nca_check_stack does (no limit on an axis); a volume has at most 2^31 - 2 nodes.  h_a = 1.0 / inv_a in f64.
+ * OPEN NODES.  cost is f32 [n_vol][n0][n1][n2].  A node is OPEN when its cost is finite and >= 0; every other node (NaN, +-inf, negative) is
+ *     a WALL.
+ * NEIGHBOURS.  conn = 1, 2 or 3: the offsets d = (d0, d1, d2) in {-1, 0, 1}^3 with 1 .. conn non-zero components (6, 18 or 26, as in
+ *     "label"), enumerated in ascending (d0, d1, d2) order.
+ * EDGES.  len(d) = sqrt(((d0 h0)^2 + (d1 h1)^2) + (d2 h2)^2);   w(u, v) = len(d) * (0.5 * ((double)cost[u] + (double)cost[v])), symmetric.
+ * DISTANCE.  dist is f64 [n_vol][n0][n1][n2], in/out.  The caller initialises it: 0 at seeds, +inf elsewhere; any non-negative field is
+ *     accepted (a run can be resumed, and re-seeded by lowering values).  Walls are written as +inf.  The fixed point is
+ *         D[v] = min(D_in[v], min over the open neighbours u of v of fl(D[u] + w(u, v)))   on the open nodes v.
+ * SWEEP.  The grid is cut into tiles of 4 x 8 x 64 nodes.  Sweep s reads state s - 1 everywhere and replaces every tile T by the fixed
+ *     point of the relaxation restricted to T, the nodes one step outside T frozen at their values of state s - 1.  State s is a function of
+ *     the input alone, converged or not.  A tile CHANGED in sweep s when a node of it has another value in state s than in state s - 1
+ *     (a wall that held a finite value counts).
+ * PREDECESSOR.  pred[v], int32: among the open neighbours u of an open v with D[u] < D[v] strictly, the linear index within the volume of
+ *     the one that minimises fl(D[u] + w(u, v)), the first in offset order on a tie; -1 when there is none (seeds, unreachable nodes, walls,
+ *     zero-weight plateaus).  Every chain strictly decreases in D: no cycles.
+ * TRACE.  From starts[p] follow pred: the nodes go to row p of paths int32 [n_paths][max_len], the tail is filled with -1, lengths[p] is
+ *     the number of nodes written.  The walk stops after writing a node whose stop byte is non-zero (status 1; stop is uint8 [voxels] or
+ *     NULL), else at a node whose pred word is outside [0, voxels) (status 0), else after max_len nodes (status 2).  A start outside
+ *     [0, voxels) writes nothing (status 3; pred holds -1 on a wall as on a seed, so a wall that is a start gives one node and status 0).
+ *     Bounded by max_len for ANY contents of pred.
+ * BALL COVER.  n_points pairs of a node index (negative or >= voxels: skipped) and an f32 radius r: covered[x] = 1 (uint8, in/out, only ever
+ *     set) for every node x of the grid with ((x0 - p0) h0)^2 + ((x1 - p1) h1)^2 + ((x2 - p2) h2)^2 <= (double)r * (double)r, the sum in
+ *     axis order, the differences exact.  A NaN radius covers nothing.  All writers write the same value: no atomics.
+ *
+ * nca_vol_geodesic: `sweeps` >= 1 sweeps, ping-pong between dist and the workspace; the result is in dist whatever the parity of sweeps
+ *     (an odd count ends with a copy).  changed int32 [n_vol] on the device: the tiles of that volume that changed in the LAST sweep; 0
+ *     means the fixed point is reached.  A workgroup brings its tile to the fixed point in LDS in rounds; it waits for no other workgroup,
+ *     and no atomics touch D: the same bits on every run.  With skipping on (nca_path_set_skip, the default) a tile is not run in a sweep
+ *     when neither it nor any of its 26 neighbour tiles changed in the sweep before (never in the first sweep of a call): the bits are the
+ *     same either way.  The workspace, with round256 as in "label" and tiles = ceil(n0 / 4) ceil(n1 / 8) ceil(n2 / 64):
+ *         round256(8 n_vol n0 n1 n2) + 2 round256(n_vol tiles) bytes.   The query returns it, and 0 for arguments the entry point refuses.
+ * nca_vol_geodesic_pred: one launch, one thread per node.   nca_vol_trace_paths: one volume, one thread per path.
+ * nca_vol_ball_cover: one volume, one workgroup per point over the ball's box clipped to the grid.
+ * NCA_E_INVALID (the message names the value): a NULL grid or pointer (stop alone may be NULL); n_vol, sweeps, voxels, n_paths, max_len
+ * or n_points <= 0; the grid refusals of nca_drr_project; more than 2^31 - 1 tiles or runs of 256 nodes in the stack (what one launch
+ * covers); nca_path_set_skip with a value that is neither 0 nor 1.   NCA_E_UNSUPPORTED: conn outside 1 .. 3; a volume of more than 2^31 - 2
+ * nodes.   NCA_E_WORKSPACE: work is NULL or work_bytes is below the query's answer.  The order: pointers, the counts and the grid, conn,
+ * sweeps, the workspace, the launch limits, the node count. */
+size_t nca_vol_geodesic_workspace(const NcaGrid* grid, int32_t n_vol);
+int nca_vol_geodesic(const NcaGrid* grid, int32_t n_vol, const float* cost, double* dist, int32_t conn, int32_t sweeps, int32_t* changed, void* work,
+                     size_t work_bytes, void* stream);
+int nca_vol_geodesic_pred(const NcaGrid* grid, int32_t n_vol, const float* cost, const double* dist, int32_t conn, int32_t* pred, void* stream);
+int nca_vol_trace_paths(int64_t voxels, const int32_t* pred, const uint8_t* stop, int32_t n_paths, const int32_t* starts, int32_t max_len, int32_t* paths,
+                        int32_t* lengths, int32_t* status, void* stream);
+int nca_vol_ball_cover(const NcaGrid* grid, int32_t n_points, const int32_t* nodes, const float* radius, uint8_t* covered, void* stream);
+int nca_path_set_skip(int32_t on);
+int nca_path_get_skip(void);
+
+/* The message of the calling thread's last failed call of this section. */
+const char* nca_path_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,3 +178,33 @@ def write_vtk(path, mesh: Mesh) -> None:
             out.write(f"POINT_DATA {v.shape[0]}\nNORMALS normals float\n".encode("ascii"))
             out.write(n.astype(">f4").tobytes())
             out.write(b"\n")
+
+
+def write_vtk_polylines(path, points, radius=None) -> None:
+    """Polylines as a legacy VTK PolyData file (binary, big-endian): ``points`` is a list of ``[n_k, 3]`` arrays or tensors, one polyline
+    each (what ``centreline.extract`` returns as ``points``) -- POINTS float, LINES with one cell per polyline, and with ``radius`` (a list of
+    ``[n_k]``) the scalar ``radius`` as POINT_DATA."""
+    def host(t):
+        return np.asarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t)
+
+    rows = [host(p).reshape(-1, 3) for p in points]
+    if radius is not None and [host(r).size for r in radius] != [p.shape[0] for p in rows]:
+        raise _capi.NcaError("write_vtk_polylines: radius has one value per point of every polyline")
+    pts = np.concatenate(rows) if rows else np.zeros((0, 3))
+    cells, first = [], 0
+    for p in rows:
+        cells.append(np.concatenate([[p.shape[0]], np.arange(first, first + p.shape[0])]))
+        first += p.shape[0]
+    cells = np.concatenate(cells).astype(">i4") if cells else np.zeros((0,), dtype=">i4")
+    with open(path, "wb") as out:
+        out.write(b"# vtk DataFile Version 3.0\ncentreline\nBINARY\nDATASET POLYDATA\n")
+        out.write(f"POINTS {pts.shape[0]} float\n".encode("ascii"))
+        out.write(pts.astype(">f4").tobytes())
+        out.write(f"\nLINES {len(rows)} {cells.size}\n".encode("ascii"))
+        out.write(cells.tobytes())
+        out.write(b"\n")
+        if radius is not None:
+            rad = np.concatenate([host(r).reshape(-1) for r in radius]) if rows else np.zeros((0,))
+            out.write(f"POINT_DATA {pts.shape[0]}\nSCALARS radius float 1\nLOOKUP_TABLE default\n".encode("ascii"))
+            out.write(rad.astype(">f4").tobytes())
+            out.write(b"\n")

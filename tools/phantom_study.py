@@ -32,7 +32,10 @@ default; metrics.keep_largest), all averaged over the phases: how much of the di
 --vesselness (with --distances, --cldice and --components) adds, after every fit, a row in which the fitted dynamic stack is replaced by
 its multi-scale Hessian vesselness (ccta.vesselness at --vesselness-sigmas, Frangi's c) before it is thresholded at a quarter of its own
 maximum, with the same columns against the same truth, and a second table that sets the two inputs side by side, with the Dice
-coefficient of the two masks.
+coefficient of the two masks.  --centreline (on its own) adds a table of the centreline TREE centreline.extract finds at phase 0 in the
+truth and in every fit, rooted at the mask node nearest the first segment's start: the share of its points within a cell diagonal of
+phantom.centreline_points and the reverse, the radius error against the table's radius at the nearest true point, and the branch count
+beside the table's leaves (profiles/phantom_study_centreline.txt).
 
 These numbers are recorded and gated nowhere.
 
@@ -103,8 +106,58 @@ def mask_dice(pred, truth, pred_threshold, threshold):
     return float((2.0 * (a & b).sum(dims).double() / (a.sum(dims).double() + b.sum(dims).double())).mean())
 
 
-def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice=None, keep=None, vesselness=None):
-    """The rows of one grid size; with `vesselness` (the sigmas) also the side-by-side rows of the fit and of its vesselness."""
+def truth_tree(table, step):
+    """(points f64 [n, 3], radius f64 [n], leaves) of ONE phase of a segment table [N, 8]: every row sampled as phantom.centreline_points
+    samples it, with the radius interpolated between the row's two; `leaves` counts the row ends that are no row's start."""
+    import numpy as np
+    pts, rad = [], []
+    for row in np.asarray(table, dtype=np.float64):
+        a, b = row[0:3], row[3:6]
+        m = max(1, int(math.ceil(float(np.linalg.norm(b - a)) / step)))
+        t = np.arange(m + 1, dtype=np.float64) / m
+        pts.append(a[None, :] + t[:, None] * (b - a)[None, :])
+        rad.append(row[6] + t * (row[7] - row[6]))
+    starts = {tuple(np.round(row[0:3], 9)) for row in np.asarray(table)}
+    leaves = sum(tuple(np.round(row[3:6], 9)) not in starts for row in np.asarray(table))
+    return np.concatenate(pts), np.concatenate(rad), leaves
+
+
+def centreline_row(vol, bounds, table, threshold, max_paths=64):
+    """The tree centreline.extract finds in ONE volume against one phase of the segment table: the root is the mask node nearest the first
+    segment's start; overlap both ways within a cell diagonal, the radius error at the nearest true point, the branch counts."""
+    from nerfca_amd import centreline
+    side = vol.shape[-1]
+    h = [(b[1] - b[0]) / (side - 1) for b in bounds]
+    tol = math.sqrt(sum(x * x for x in h))
+    true_pts, true_rad, leaves = truth_tree(table, 0.5 * min(h))
+    mask = vol > threshold
+    if not bool(mask.any()):
+        return {"branches": 0, "branches_truth": leaves, "empty_mask": True}
+    idx = mask.nonzero().to(torch.float64)
+    world = torch.tensor([b[0] for b in bounds], dtype=torch.float64, device=vol.device) + idx * torch.tensor(h, dtype=torch.float64, device=vol.device)
+    start = torch.tensor(table[0][0:3], dtype=torch.float64, device=vol.device)
+    gap = (world - start).norm(dim=1)
+    root = tuple(float(v) for v in world[int(gap.argmin())])
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    c = centreline.extract(vol, bounds, threshold=threshold, root=root, max_paths=max_paths)
+    torch.cuda.synchronize()
+    seconds = time.perf_counter() - t0
+    found = torch.cat(c.points).to(torch.float64)
+    truth = torch.tensor(true_pts, device=vol.device)
+    found_near, truth_near = centreline.overlap(found, truth, tol)
+    d = torch.cdist(found, truth)
+    near, which = d.min(dim=1)
+    ok = near <= tol
+    err = (torch.cat(c.radius).to(torch.float64) - torch.tensor(true_rad, device=vol.device)[which]).abs()[ok]
+    return {"branches": len(c.paths), "branches_truth": leaves, "total_length": float(sum(c.length)), "reached": c.reached, "root_gap_cells": float(gap.min()) / max(h),
+            "found_within_diagonal_of_truth": found_near, "truth_within_diagonal_of_found": truth_near,
+            "radius_error_mean_cells": float(err.mean()) / max(h) if int(ok.sum()) else math.nan, "extract_seconds": round(seconds, 3)}
+
+
+def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice=None, keep=None, vesselness=None, centreline=None):
+    """The rows of one grid size; with `vesselness` (the sigmas) also the side-by-side rows of the fit and of its vesselness; with
+    `centreline` (a list) the centreline rows of the truth and of every fit, at phase 0, are appended to it."""
     from nerfca_amd import ccta, drr, metrics, phantom, synthetic
     geo = synthetic.xcat_geometry(n_det)
     ph = phantom.make_phantom((side,) * 3, PHASES, geo, device=dev)
@@ -115,6 +168,9 @@ def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice
     frames = [(theta, phi, p, train[v, p].contiguous()) for v, (theta, phi) in enumerate(views) for p in range(PHASES)]
     threshold = 0.25 * phantom.RHO_VESSEL
     rows, pairs = [], []
+    if centreline is not None:
+        centreline.append({"volume": side, "input": "truth", **centreline_row(dynamic[0], bounds, ph["segments"][0], threshold)})
+        print(json.dumps(centreline[-1]), flush=True)
     held_range = held.amax(dim=(-2, -1)).double() - held.amin(dim=(-2, -1)).double()
     for tv_space, tv_time, *rest in weights:
         ssim_weight = rest[0] if rest else 0.0
@@ -138,6 +194,11 @@ def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice
         if "ssim" in fit:
             rows[-1].update({"ssim_train_first": fit["ssim"][0], "ssim_train_last": fit["ssim"][-1]})
         print(json.dumps(rows[-1]), flush=True)
+        if centreline is not None:
+            own = 0.25 * float(fit["dynamic"].max())
+            centreline.append({"volume": side, "input": "fit", "tv_space": tv_space, "tv_time": tv_time, "ssim_weight": ssim_weight, "dice_vessels": e_d["dice"],
+                               **centreline_row(fit["dynamic"][0].contiguous(), bounds, ph["segments"][0], own)})
+            print(json.dumps(centreline[-1]), flush=True)
         if vesselness:
             V = ccta.vesselness(fit["dynamic"], vesselness)
             for name, x in (("density", fit["dynamic"]), ("vesselness", V)):
@@ -184,6 +245,7 @@ def parser():
     ap.add_argument("--components", action="store_true", help="with --distances: add the component count, the largest component's share and the distances of the cleaned mask")
     ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="with --components: the cleaned mask keeps the K largest components (default 1)")
     ap.add_argument("--vesselness", action="store_true", help="with --distances --cldice K --components: add rows for the vesselness of the fitted dynamic stack")
+    ap.add_argument("--centreline", action="store_true", help="add rows for the centreline tree (centreline.extract) of the truth and of every fit, at phase 0")
     ap.add_argument("--vesselness-sigmas", default="1,2,3", help="its scales in nodes, comma separated")
     return ap
 
@@ -208,8 +270,9 @@ def main(argv=None):
     sides = tuple(int(s) for s in args.sides.split(","))
     ssim_weights = [float(w) for w in args.ssim_weight.split(",") if w.strip()]
     fits, pairs = [], []
+    lines = [] if args.centreline else None
     for side in sides:
-        rows, both = study(dev, side, args.n_det, args.samples, args.steps, args.lr, WEIGHTS + ssim_rows(ssim_weights), args.distances, args.cldice, keep, vess_sigmas)
+        rows, both = study(dev, side, args.n_det, args.samples, args.steps, args.lr, WEIGHTS + ssim_rows(ssim_weights), args.distances, args.cldice, keep, vess_sigmas, lines)
         fits += rows
         pairs += both
         torch.cuda.empty_cache()
@@ -232,13 +295,24 @@ def main(argv=None):
         for r in pairs:
             table.append(f"{r['volume']:>4}^3  {r['tv_space']:<8g}  {r['tv_time']:<7g}  {r['input']:<10}  {r['input_max']:>8.4f}   {r['dice_own_quarter']:.4f}      {r['assd_cells']:>7.3f}       {r['hd95_cells']:>7.3f}       "
                          f"{r['cldice']:.4f}         {r['components']:>8.1f} ({r['components_truth']:.1f})       {r['largest_share']:.4f}        {r['centreline_coverage']:.4f}")
+    if lines:
+        table.append("the centreline tree (centreline.extract, at most 64 paths, root: the mask node nearest the first segment's start) of phase 0 of the truth > rho / 4 and of every "
+                     "fit > a quarter of its own maximum, against the segment table: points within a cell diagonal, both ways")
+        table.append("volume  input  tv_space  tv_time  Dice >rho/4  branches (truth)  found near truth  truth near found  radius error (cells)  length    reached  root gap (cells)  seconds")
+        for r in lines:
+            if r.get("empty_mask"):
+                table.append(f"{r['volume']:>4}^3  {r['input']:<5}  empty mask")
+                continue
+            table.append(f"{r['volume']:>4}^3  {r['input']:<5}  {r.get('tv_space', 0.0):<8g}  {r.get('tv_time', 0.0):<7g}  {r.get('dice_vessels', 1.0):>10.4f}   {r['branches']:>6} ({r['branches_truth']})"
+                         f"        {r['found_within_diagonal_of_truth']:.4f}            {r['truth_within_diagonal_of_found']:.4f}            {r['radius_error_mean_cells']:>8.3f}         "
+                         f"{r['total_length']:>8.3f}  {r['reached']:.4f}   {r['root_gap_cells']:>8.3f}        {r['extract_seconds']:>8.3f}")
     table.append(f"reprojection distance: the frames of the phantom rasterised at n^3 against those of the phantom at {FINE}^3 (4 views x {PHASES} phases)")
     for r in rep:
         table.append(f"{r['volume']:>4}^3   " + "   ".join(f"{k}: max {r[k]['max_abs']:.4e} rmse {r[k]['rmse']:.4e} PSNR {r[k]['psnr']:.2f} dB" for k in ("pred", "pred_static", "pred_dynamic")))
     print("\n".join(table))
     if args.out:
         with open(args.out, "w") as f:
-            for r in fits + pairs + rep:
+            for r in fits + pairs + (lines or []) + rep:
                 f.write(json.dumps(r) + "\n")
             f.write("\n".join(table) + "\n")
 
