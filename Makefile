@@ -8,7 +8,7 @@ SRCS  := $(CSRC)/nca_api.hip $(CSRC)/nca_kernels_f32.hip $(CSRC)/nca_kernels_bf1
          $(CSRC)/view/nca_view.hip $(CSRC)/view/nca_drr.hip $(CSRC)/view/nca_voltv.hip $(CSRC)/view/nca_phantom.hip \
          $(CSRC)/view/nca_ssim.hip $(CSRC)/view/nca_edt.hip $(CSRC)/view/nca_filt.hip \
          $(CSRC)/view/nca_resample.hip $(CSRC)/view/nca_skel.hip $(CSRC)/view/nca_label.hip $(CSRC)/view/nca_vess.hip \
-         $(CSRC)/view/nca_mesh.hip $(CSRC)/view/nca_path.hip
+         $(CSRC)/view/nca_mesh.hip $(CSRC)/view/nca_path.hip $(CSRC)/view/nca_cpr.hip
 HDRS  := include/nerfca_hip.h $(CSRC)/nca_layout.hpp $(CSRC)/nca_kernels.hpp $(CSRC)/nca_rng.hpp
 OBJS  := $(SRCS:.hip=.o)
 FLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function

@@ -1187,6 +1187,71 @@ int nca_path_get_skip(void);
 /* The message of the calling thread's last failed call of this section. */
 const char* nca_path_last_error(void);
 
+/* ---- cpr: oblique planes and lumen rays through voxel stacks (reformat.cross_sections / lumen_profile) -----------------------------------------
+ * The gathers of a curved-planar reformation and of a lumen profile along a centreline: many small planes, or fans of rays in such planes,
+ * through a stack of volumes on one NcaGrid.  Purely additive to ABI 13.  Like the other view sections these entry points keep their OWN
+ * per-thread message (the accessor below); a refused call launches nothing and reads no device pointer; a launch failure is reported once.
+ * Every entry point launches on `stream` and nothing else and reads nothing back.  Every f64 operation below is ONE rounded operation in the
+ * order written (no fused multiply-add anywhere; the kernels spell each one out), so a transcription into any IEEE arithmetic has the same
+ * bits.  `grid` is a host pointer; every other pointer is on the device.
+ *
+ * PLANES.  n_planes planes: origin, e1 and e2 are f64 [n_planes][3], in world coordinates.  Nothing checks that e1 and e2 are orthonormal:
+ *     they are used as given.
+ * WORLD TO GRID.  For a world point p:  x_a = (p_a - lo_a) * inv_a.  The point is INSIDE when 0 <= x_a <= n_a - 1 on all three axes, the
+ *     comparisons as written: a NaN coordinate is outside.
+ * ORDER 1 (the value g(p) of an inside point in a stack of f32 nodes):  f_a = min(floor(x_a), n_a - 2);   y_a = x_a - f_a;   the eight nodes
+ *     (f_0 + a, f_1 + b, f_2 + c), a, b, c in {0, 1}, widened to f64; a pair (lo: offset 0, hi: offset 1) is combined as
+ *         lo + y * (hi - lo)                                                       (three operations)
+ *     along axis 2 (four pairs, y_2), then along axis 1 (two pairs of those results, y_1), then along axis 0 (y_0).  With y = 0 the result
+ *     is lo, and with y = 1 (the last node of an axis, where f = n - 2) it is hi, whenever hi - lo is finite and exact in f64 -- for f32
+ *     nodes: whenever both are finite and their exponents lie within 29 of each other -- so a point on a node returns that node's value.
+ * ORDER 3 (a stack of f64 coefficients, what nca_vol_spline_filter writes):  per axis cc = x_a, then f, y, t, the weights w0 .. w3, the
+ *     mirrored taps j = M(f - 1 + k) and the lexicographic accumulation acc exactly as under INTERPOLATION of the "resample" section.
+ *
+ * nca_vol_sample_planes: out is f32 [n_vol][n_planes][nu][nv].  Pixel (i, j) of plane k:
+ *         u = ((double)i - 0.5 * (double)(nu - 1)) * du;      v = ((double)j - 0.5 * (double)(nv - 1)) * dv;
+ *         p_a = (origin[k][a] + u * e1[k][a]) + v * e2[k][a].
+ *     A point that is not inside gives `fill` (any f32, its bits kept).  Else, per volume q:
+ *     order 0: src is the f32 stack [n_vol][n0][n1][n2]; out = the node floor(x_a + 0.5) per axis: exact, a NaN or an infinity included.
+ *     order 1: src is the f32 stack; out = (float)g(p): the one rounding to f32.
+ *     order 3: src is the f64 coefficient stack; out = (float)acc.
+ *     One thread per pixel, a workgroup per tile of 16 x 16 pixels of one plane.  The coordinates, tap indices and weights of a pixel are
+ *     formed once and reused for all n_vol volumes.  Every output is written once by one thread: no atomics, the same bits on every run.
+ * nca_vol_lumen: vol is the f32 stack; dirs is f64 [n_ang][2], the host's (cos, sin) of 2 pi a / n_ang, and sin_step the host's
+ *     sin(2 pi / n_ang): both are inputs, no transcendental is evaluated on the device.  Ray a of plane k in volume q takes the samples
+ *     j = 0 .. n_steps:
+ *         r_j = (double)j * dr;   c = r_j * dirs[a][0];   s = r_j * dirs[a][1];   p_a = (origin[k][a] + c * e1[k][a]) + s * e2[k][a];
+ *         g_j = g(p), order 1, kept in f64.
+ *     The ray ends at the first j at which
+ *         the sample is not inside:   r = r_{j-1} (0 at j = 0), status bit 4;   or else
+ *         !(g_j > level):   at j = 0   r = 0 and status bit 1 (the centre is not in the lumen);
+ *                           at j > 0   t = (g_{j-1} - level) / (g_{j-1} - g_j), t = 0 when g_j is not finite;   r = ((double)(j - 1) + t) * dr.
+ *     If no sample ends it:   r = (double)n_steps * dr, status bit 2 (open).
+ *     radius f32 [n_vol][n_planes][n_ang] = (float)r.   status int32 [n_vol][n_planes] = the OR of the bits of the plane's rays.
+ *     stats f64 [n_vol][n_planes][4], from the unrounded r, every sum starting at 0 and taken in ascending a:
+ *         [0] area = (0.5 * sin_step) * sum_a r_a * r_{(a + 1) mod n_ang}             (the polygon through the ray ends)
+ *         [1] the minimum and [2] the maximum of D_a = r_a + r_{a + n_ang / 2}, a = 0 .. n_ang / 2 - 1, each starting from D_0 and replaced
+ *             when D_a < min (D_a > max) holds
+ *         [3] mean = (sum_a r_a) / (double)n_ang.
+ *     One workgroup per (volume, plane): a thread per ray (looping when n_ang exceeds the workgroup's 256 threads), the unrounded r in LDS,
+ *     the sums by one thread each in the stated order.  No workgroup waits for another and no atomics touch global memory: the same bits
+ *     on every run.
+ * NCA_E_INVALID (the message names the value): a NULL grid or pointer; n_vol, n_planes, nu, nv or n_steps <= 0; the grid refusals of
+ * nca_drr_project (the node count taken at 8 bytes per node); a du, dv or dr that is not finite and positive; a sin_step that is not finite;
+ * a NaN level; n_ang odd or below 4; more than 2^31 - 1 workgroups, or outputs whose bytes overflow int64 (what one launch covers).
+ * NCA_E_UNSUPPORTED: order outside {0, 1, 3}; n_ang above NCA_CPR_MAX_ANGLES.
+ * The order: the pointers as the arguments list them; n_vol and the grid; then order, n_planes, nu, nv, du, dv (planes) or n_planes, n_ang,
+ * n_steps, sin_step, level, dr (lumen); the launch limits last. */
+enum { NCA_CPR_MAX_ANGLES = 1024, NCA_CPR_STATUS_CENTRE = 1, NCA_CPR_STATUS_OPEN = 2, NCA_CPR_STATUS_GRID = 4 };
+int nca_vol_sample_planes(const NcaGrid* grid, int32_t n_vol, const void* src, int32_t order, int32_t n_planes, const double* origin, const double* e1,
+                          const double* e2, int32_t nu, int32_t nv, double du, double dv, float fill, float* out, void* stream);
+int nca_vol_lumen(const NcaGrid* grid, int32_t n_vol, const float* vol, int32_t n_planes, const double* origin, const double* e1, const double* e2,
+                  int32_t n_ang, const double* dirs, double sin_step, double level, double dr, int32_t n_steps, float* radius, double* stats,
+                  int32_t* status, void* stream);
+
+/* The message of the calling thread's last failed call of this section. */
+const char* nca_cpr_last_error(void);
+
 #ifdef __cplusplus
 }
 #endif

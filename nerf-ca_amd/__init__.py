@@ -11,5 +11,6 @@ from . import metrics  # noqa: F401
 from . import ccta  # noqa: F401
 from . import mesh  # noqa: F401
 from . import centreline  # noqa: F401
+from . import reformat  # noqa: F401
 
-__all__ = ["render_rays", "eval_points", "set_precision", "drr", "phantom", "metrics", "ccta", "mesh", "centreline"]
+__all__ = ["render_rays", "eval_points", "set_precision", "drr", "phantom", "metrics", "ccta", "mesh", "centreline", "reformat"]

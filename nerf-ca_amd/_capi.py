@@ -265,6 +265,9 @@ SYMBOLS = {
     "nca_path_set_skip": (C.c_int, [_I32]),
     "nca_path_get_skip": (C.c_int, []),
     "nca_path_last_error": (C.c_char_p, []),
+    "nca_vol_sample_planes": (C.c_int, [C.POINTER(NcaGrid), _I32, _P, _I32, _I32, _P, _P, _P, _I32, _I32, C.c_double, C.c_double, C.c_float, _P, _P]),          # ("cpr": after "path" in the header)
+    "nca_vol_lumen": (C.c_int, [C.POINTER(NcaGrid), _I32, _P, _I32, _P, _P, _P, _I32, _P, C.c_double, C.c_double, C.c_double, _I32, _P, _P, _P, _P]),
+    "nca_cpr_last_error": (C.c_char_p, []),
     "nca_vol_hessian_eig": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, _P, _P]),
     "nca_vol_hessian_norm_max": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, _P, _P]),
     "nca_vol_vesselness": (C.c_int, [C.POINTER(NcaGrid), _P, _I32, C.c_double, C.c_double, C.c_double, _P, _I32, _I32, _P, _P, _P]),
@@ -319,6 +322,7 @@ check_skel = _section_check("nca_skel_last_error", "soft-skeleton entry points (
 check_label = _section_check("nca_label_last_error", "connected-component entry points (nca_vol_label*)")
 check_mesh = _section_check("nca_mesh_last_error", "iso-surface entry points (nca_vol_iso_*)")
 check_path = _section_check("nca_path_last_error", "minimal-path entry points (nca_vol_geodesic*, nca_vol_trace_paths, nca_vol_ball_cover, nca_path_*)")
+check_cpr = _section_check("nca_cpr_last_error", "reformation entry points (nca_vol_sample_planes, nca_vol_lumen)")
 check_vess = _section_check("nca_vess_last_error", "vesselness entry points (nca_vol_hessian_*, nca_vol_vesselness)")
 
 

@@ -1,6 +1,6 @@
 // nca_view_common.hpp -- what the translation units of csrc/view/ share (internal; nothing here is exported): the error message of a
-// section; for the twelve grid-taking sections (drr project and backproject, vol, phantom, edt, filt, resample, skel, label, vess, mesh, path) the refusals of a NULL descriptor
-// and of a count that is not positive and the NcaGrid checks, and all of them in order as nca_check_stack (edt, filt, resample, skel, label, vess, mesh, path; the first five's, mesh's and path's query and
+// section; for the thirteen grid-taking sections (drr project and backproject, vol, phantom, edt, filt, resample, skel, label, vess, mesh, path, cpr) the refusals of a NULL descriptor
+// and of a count that is not positive and the NcaGrid checks, and all of them in order as nca_check_stack (edt, filt, resample, skel, label, vess, mesh, path, cpr; the first five's, mesh's and path's query and
 // entry point share them); the count of 4 x 8 x 64 tiles (vol, phantom, skel, label, vess, mesh, path); the largest of three launches' block counts against one launch's limit
 // (edt, filt, resample; skel and vess with one count, label, mesh and path with one or two); the workspace refusal (ssim, edt, filt, resample, skel, label, mesh, path); and, for hipcc only, the launch epilogue and
 // the tile's indexing on the device.  The Python wrappers' counterpart is nerf-ca_amd/_view.py.  Every text below is part of the library's behaviour: tests and callers

@@ -35,7 +35,12 @@ maximum, with the same columns against the same truth, and a second table that s
 coefficient of the two masks.  --centreline (on its own) adds a table of the centreline TREE centreline.extract finds at phase 0 in the
 truth and in every fit, rooted at the mask node nearest the first segment's start: the share of its points within a cell diagonal of
 phantom.centreline_points and the reverse, the radius error against the table's radius at the nearest true point, and the branch count
-beside the table's leaves (profiles/phantom_study_centreline.txt).
+beside the table's leaves (profiles/phantom_study_centreline.txt).  --lumen (on its own) adds a table of LUMEN DIAMETERS: along every
+chain of segments of the table (tools/cpr_bench.py segment_chains; reformat.frames of the chain's joints at half a node spacing), at every
+heart phase, reformat.lumen_profile of the truth at rho / 4 and of every fit at a quarter of its own maximum (64 rays out to four times the
+largest radius of the table): the mean absolute error of d_eq / 2 against the table's radius at the plane, in node spacings, over the
+planes of status 0, and the share of such planes (profiles/phantom_study_lumen.txt).  The phantom's wall is a ramp one node spacing wide,
+centred on the table's radius, so at rho / 4 the truth itself reads a quarter of a spacing wide.
 
 These numbers are recorded and gated nowhere.
 
@@ -155,9 +160,36 @@ def centreline_row(vol, bounds, table, threshold, max_paths=64):
             "radius_error_mean_cells": float(err.mean()) / max(h) if int(ok.sum()) else math.nan, "extract_seconds": round(seconds, 3)}
 
 
-def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice=None, keep=None, vesselness=None, centreline=None):
+def lumen_row(stack, bounds, segments, level):
+    """reformat.lumen_profile of the stack [P, n, n, n] along every chain of the segment table [P, N, 8], phase by phase, against the table's
+    radius: the mean |d_eq / 2 - radius| over the planes of status 0 in node spacings, the mean signed error, and the share of such planes."""
+    import numpy as np
+    from nerfca_amd import reformat
+    from tools.cpr_bench import segment_chains
+    side = stack.shape[-1]
+    h = [(b[1] - b[0]) / (side - 1) for b in bounds]
+    r_max = 4.0 * float(np.asarray(segments)[..., 6:8].max())
+    err, signed, ok, planes = 0.0, 0.0, 0, 0
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for p in range(stack.shape[0]):
+        for joints, radius in segment_chains(segments[p]):
+            fr = reformat.frames(joints, step=0.5 * min(h))
+            at = np.concatenate([[0.0], np.cumsum(np.sqrt(((joints[1:] - joints[:-1]) ** 2).sum(1)))])
+            want = torch.tensor(np.interp(fr.s, at, radius), device=stack.device)
+            prof = reformat.lumen_profile(stack[p], bounds, fr, level=level, r_max=r_max, n_angles=64)
+            good = prof.status == 0
+            d = (0.5 * prof.d_eq - want)[good]
+            err, signed, ok, planes = err + float(d.abs().sum()), signed + float(d.sum()), ok + int(good.sum()), planes + good.numel()
+    torch.cuda.synchronize()
+    return {"lumen_planes": planes, "lumen_status0_share": ok / planes, "lumen_radius_mae_cells": err / ok / max(h) if ok else math.nan,
+            "lumen_radius_bias_cells": signed / ok / max(h) if ok else math.nan, "lumen_seconds": round(time.perf_counter() - t0, 3)}
+
+
+def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice=None, keep=None, vesselness=None, centreline=None, lumen=None):
     """The rows of one grid size; with `vesselness` (the sigmas) also the side-by-side rows of the fit and of its vesselness; with
-    `centreline` (a list) the centreline rows of the truth and of every fit, at phase 0, are appended to it."""
+    `centreline` (a list) the centreline rows of the truth and of every fit, at phase 0, are appended to it; with `lumen` (a list) the lumen
+    rows of the truth and of every fit, over all phases."""
     from nerfca_amd import ccta, drr, metrics, phantom, synthetic
     geo = synthetic.xcat_geometry(n_det)
     ph = phantom.make_phantom((side,) * 3, PHASES, geo, device=dev)
@@ -171,6 +203,9 @@ def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice
     if centreline is not None:
         centreline.append({"volume": side, "input": "truth", **centreline_row(dynamic[0], bounds, ph["segments"][0], threshold)})
         print(json.dumps(centreline[-1]), flush=True)
+    if lumen is not None:
+        lumen.append({"volume": side, "input": "truth", "level": threshold, **lumen_row(dynamic, bounds, ph["segments"], threshold)})
+        print(json.dumps(lumen[-1]), flush=True)
     held_range = held.amax(dim=(-2, -1)).double() - held.amin(dim=(-2, -1)).double()
     for tv_space, tv_time, *rest in weights:
         ssim_weight = rest[0] if rest else 0.0
@@ -199,6 +234,11 @@ def study(dev, side, n_det, samples, steps, lr, weights, distances=False, cldice
             centreline.append({"volume": side, "input": "fit", "tv_space": tv_space, "tv_time": tv_time, "ssim_weight": ssim_weight, "dice_vessels": e_d["dice"],
                                **centreline_row(fit["dynamic"][0].contiguous(), bounds, ph["segments"][0], own)})
             print(json.dumps(centreline[-1]), flush=True)
+        if lumen is not None:
+            own = 0.25 * float(fit["dynamic"].max())
+            lumen.append({"volume": side, "input": "fit", "tv_space": tv_space, "tv_time": tv_time, "ssim_weight": ssim_weight, "dice_vessels": e_d["dice"], "level": own,
+                          **lumen_row(fit["dynamic"].contiguous(), bounds, ph["segments"], own)})
+            print(json.dumps(lumen[-1]), flush=True)
         if vesselness:
             V = ccta.vesselness(fit["dynamic"], vesselness)
             for name, x in (("density", fit["dynamic"]), ("vesselness", V)):
@@ -246,6 +286,7 @@ def parser():
     ap.add_argument("--keep-largest", type=int, default=None, metavar="K", help="with --components: the cleaned mask keeps the K largest components (default 1)")
     ap.add_argument("--vesselness", action="store_true", help="with --distances --cldice K --components: add rows for the vesselness of the fitted dynamic stack")
     ap.add_argument("--centreline", action="store_true", help="add rows for the centreline tree (centreline.extract) of the truth and of every fit, at phase 0")
+    ap.add_argument("--lumen", action="store_true", help="add rows for the lumen radius (reformat.lumen_profile) of the truth and of every fit along the segment table's chains, all phases")
     ap.add_argument("--vesselness-sigmas", default="1,2,3", help="its scales in nodes, comma separated")
     return ap
 
@@ -271,8 +312,9 @@ def main(argv=None):
     ssim_weights = [float(w) for w in args.ssim_weight.split(",") if w.strip()]
     fits, pairs = [], []
     lines = [] if args.centreline else None
+    lumen = [] if args.lumen else None
     for side in sides:
-        rows, both = study(dev, side, args.n_det, args.samples, args.steps, args.lr, WEIGHTS + ssim_rows(ssim_weights), args.distances, args.cldice, keep, vess_sigmas, lines)
+        rows, both = study(dev, side, args.n_det, args.samples, args.steps, args.lr, WEIGHTS + ssim_rows(ssim_weights), args.distances, args.cldice, keep, vess_sigmas, lines, lumen)
         fits += rows
         pairs += both
         torch.cuda.empty_cache()
@@ -306,13 +348,20 @@ def main(argv=None):
             table.append(f"{r['volume']:>4}^3  {r['input']:<5}  {r.get('tv_space', 0.0):<8g}  {r.get('tv_time', 0.0):<7g}  {r.get('dice_vessels', 1.0):>10.4f}   {r['branches']:>6} ({r['branches_truth']})"
                          f"        {r['found_within_diagonal_of_truth']:.4f}            {r['truth_within_diagonal_of_found']:.4f}            {r['radius_error_mean_cells']:>8.3f}         "
                          f"{r['total_length']:>8.3f}  {r['reached']:.4f}   {r['root_gap_cells']:>8.3f}        {r['extract_seconds']:>8.3f}")
+    if lumen:
+        table.append("the lumen radius d_eq / 2 (reformat.lumen_profile, 64 rays, planes every half node spacing along every chain of the segment table, all phases) of the truth at rho / 4 "
+                     "and of every fit at a quarter of its own maximum, against the table's radius at the plane; planes with a status bit set are left out")
+        table.append("volume  input  tv_space  tv_time  Dice >rho/4  level      planes  status 0 share  |radius error| (cells)  signed (cells)  seconds")
+        for r in lumen:
+            table.append(f"{r['volume']:>4}^3  {r['input']:<5}  {r.get('tv_space', 0.0):<8g}  {r.get('tv_time', 0.0):<7g}  {r.get('dice_vessels', 1.0):>10.4f}   {r['level']:<9.4g}  {r['lumen_planes']:>6}  "
+                         f"{r['lumen_status0_share']:>12.4f}   {r['lumen_radius_mae_cells']:>20.3f}   {r['lumen_radius_bias_cells']:>12.3f}   {r['lumen_seconds']:>8.3f}")
     table.append(f"reprojection distance: the frames of the phantom rasterised at n^3 against those of the phantom at {FINE}^3 (4 views x {PHASES} phases)")
     for r in rep:
         table.append(f"{r['volume']:>4}^3   " + "   ".join(f"{k}: max {r[k]['max_abs']:.4e} rmse {r[k]['rmse']:.4e} PSNR {r[k]['psnr']:.2f} dB" for k in ("pred", "pred_static", "pred_dynamic")))
     print("\n".join(table))
     if args.out:
         with open(args.out, "w") as f:
-            for r in fits + pairs + (lines or []) + rep:
+            for r in fits + pairs + (lines or []) + (lumen or []) + rep:
                 f.write(json.dumps(r) + "\n")
             f.write("\n".join(table) + "\n")
 
